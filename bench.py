@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py - headline benchmark of the MI355X-native Distributed-IB training path.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak]
+    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 and no launcher environment: bench.py re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`, one rank per GPU, RCCL
@@ -23,6 +23,10 @@ torch.cuda.synchronize() on both sides, max over ranks; `value` is the MEDIAN bl
 6-8 %, so a single block is noisy); all blocks are listed.  These blocks run WITHOUT per-kernel event timing.  One more
 K-step block then runs with HIP events around every MFMA kernel (inside libdib_hip.so, on the launch stream) for the
 `roofline` of the dominant kernel; its step time is reported as `ms_per_step_kernel_timing`.
+
+`--dump-outputs DIR`: after the timed blocks (before the kernel-timing block and any `extra`), rank 0 writes what the headline
+step computed in its last step as DIR/<name>.npy (see dump_outputs); the inputs are fixed (seeded data, init_seed=0,
+noise seed 0), so two builds run with the same arguments can be compared output for output.
 
 One JSON line on rank 0 with `roofline`, `cpu_baseline` (PyTorch-CPU eager restatement of the TF graph,
 oracle/dib_torch_cpu.py, timed on this box's host cores on a bounded sample; N=1 only) and `extra` (BASELINE config 4,
@@ -76,6 +80,35 @@ def synthetic(n_rows, n_features=64, seed=20241008):
     w = rng.standard_normal(8).astype(np.float32)
     y = ((x[:, :8] @ w + 0.5 * x[:, 0] * x[:, 1]) > 0).astype(np.float32)[:, None]
     return x, y
+
+
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: at most this much in all
+
+
+def dump_outputs(wl, out_dir):
+    """What a caller of the timed step receives after its last step, as DIR/<name>.npy: the updated flat parameters, the
+    flat gradient of that step, its per-step scalars (ws[STEP_OUT]: per-feature KL sums, task-loss sum, #correct, rows)
+    and the History metric sums accumulated over every step so far.  float32 as computed (metrics: float64).  An array that
+    would push the total past DUMP_LIMIT_BYTES is replaced by a fixed, seeded sample of its elements (same indices every
+    run).  Returns {name: [shape, dtype, sampled]}.  (The CPU test of this function passes the float64 test engine.)"""
+    eng = wl.eng
+    wl._sync()
+    arrays = {"params": eng.get_flat_params()[: eng.n_params],
+              "grads": eng.grads.detach().cpu().numpy()[: eng.n_params],
+              "step_out": eng.step_out(wl.B).detach().cpu().numpy().astype(np.float32),
+              "metrics": eng.read_metrics(reset=False)}
+    os.makedirs(out_dir, exist_ok=True)
+    budget, info = DUMP_LIMIT_BYTES, {}
+    for name in sorted(arrays, key=lambda k: arrays[k].nbytes):
+        a = np.ascontiguousarray(arrays[name])
+        sampled = a.nbytes > budget
+        if sampled:
+            idx = np.sort(np.random.default_rng(20241008).choice(a.size, budget // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        budget -= a.nbytes
+        info[name] = [list(a.shape), str(a.dtype), bool(sampled)]
+    return info
 
 
 def gemm_flops_per_sample(n_features, in_dim=5):
@@ -671,6 +704,8 @@ def main():
     ap.add_argument("--only-dp-breakdown", action="store_true",
                     help="with --force-dp-extras: the data-parallel breakdown is the only extra (the per-GPU operating point, "
                          "e.g. --batch 8192 under one RCCL rank)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed blocks, write what the last timed step computed as DIR/<name>.npy (bench.dump_outputs)")
     ap.add_argument("--dry-run-backend", default=None, help=argparse.SUPPRESS)  # CPU test of the launcher path (gloo)
     args = ap.parse_args()
 
@@ -725,6 +760,7 @@ def main():
     flops_per_sample = gemm_flops_per_sample(args.features)
     eng = wl.eng
     med, times = wl.measure(args.warmup, args.steps, args.blocks, dev)
+    dumped = dump_outputs(wl, args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     # one more block with HIP events around every MFMA kernel (roofline of the dominant kernel)
     prof, t_prof = None, None
@@ -756,6 +792,8 @@ def main():
                "step_roofline": {"bound": "mfma", "achieved": round(per_gpu_tf, 3), "peak": PEAK_F32_MFMA_TFLOPS,
                                  "unit": "TFLOP/s", "frac": round(per_gpu_tf / PEAK_F32_MFMA_TFLOPS, 4),
                                  "note": "whole-step algorithmic GEMM FLOPs / wall time, per GPU"}}
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if prof:
             out["ms_per_step_kernel_timing"] = round(1e3 * t_prof / args.steps, 4)
             per, rest = per_kernel_roofline(prof, args.features, B, args.steps)

@@ -87,6 +87,7 @@ class OracleEngine:
                    on_integration_grads_ready=None, on_encoder_front_grads_ready=None, optimizer=None):
         inv = 1.0 / batch if inv_global_batch is None else inv_global_batch
         rows, xb, c = self._fwd(x, row_idx, row0, batch, seed, step)
+        self._pred, self._kl = c.pred, c.kl
         yb = y.numpy()[rows]
         task, g, _ = orc.backward(self.spec, self.p, xb, yb, c, self.beta, loss_kind,
                                   loss_scale_rows=int(round(1.0 / inv)))

@@ -1,7 +1,7 @@
-"""Generates tests/golden/ctw_golden.npz from the REFERENCE's own CTW source (compiled where it lies by
-oracle/Makefile into oracle/_ref/libctw_ref.so).  Run here, where /root/reference exists:
+"""Generates tests/golden/ctw_golden.npz and tests/golden/ctw_random_cases.npz from the REFERENCE's own CTW source
+(compiled where it lies by oracle/Makefile into oracle/_ref/libctw_ref.so).  Run here, where /root/reference exists:
     make -C oracle && python tests/golden/make_golden_ctw.py
-The fixture travels to machines without the reference (GPU box)."""
+The fixtures travel to machines without the reference (GPU box)."""
 import ctypes
 import os
 
@@ -37,12 +37,34 @@ def cases():
     return out
 
 
-if __name__ == "__main__":
-    cs = cases()
+def random_cases():
+    """40 random / periodic / skewed sequences (tests/test_ctw.py::test_against_live_reference_build_when_present)."""
+    rng = np.random.default_rng(77)
+    out = []
+    for _ in range(40):
+        a = int(rng.integers(1, 20))
+        n = int(rng.integers(1, 30000))
+        kind = rng.integers(0, 3)
+        if kind == 0:
+            s = rng.integers(0, a, n)
+        elif kind == 1:
+            s = np.tile(rng.integers(0, a, int(rng.integers(1, 50))), n // 10 + 1)[:n]      # periodic
+        else:
+            s = np.minimum((rng.random(n) ** 3 * a).astype(int), a - 1)                     # skewed
+        out.append((s, a))
+    return out
+
+
+def save(cs, name):
     flat = np.concatenate([np.asarray(s, dtype=np.int8) for s, _ in cs])
     offsets = np.concatenate([[0], np.cumsum([len(s) for s, _ in cs])]).astype(np.int64)
     alph = np.array([a for _, a in cs], dtype=np.int32)
     rates = np.array([ref_rate(s, a) for s, a in cs], dtype=np.float64)
-    np.savez_compressed(os.path.join(ROOT, "tests", "golden", "ctw_golden.npz"), symbols=flat, offsets=offsets,
+    np.savez_compressed(os.path.join(ROOT, "tests", "golden", name), symbols=flat, offsets=offsets,
                         alphabet=alph, rate=rates)
-    print(len(cs), "cases;", "rates[:5] =", rates[:5])
+    print(name, len(cs), "cases;", "rates[:5] =", rates[:5])
+
+
+if __name__ == "__main__":
+    save(cases(), "ctw_golden.npz")
+    save(random_cases(), "ctw_random_cases.npz")

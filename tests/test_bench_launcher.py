@@ -133,3 +133,45 @@ def test_bench_data_parallel_step_equals_single_process(tmp_path, world):
     mp.spawn(_bench_dp_worker, args=(world, port(), str(tmp_path), 3, "weak"), nprocs=world, join=True)
     got = [np.load(tmp_path / f"p_weak_w{world}_b3_r{r}.npy") for r in range(world)]
     assert all(np.array_equal(g, got[0]) for g in got[1:]) and np.isfinite(got[0]).all()
+
+
+def test_dump_outputs_writes_the_last_steps_arrays_within_the_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: after the timed steps the arrays of the last step land as DIR/<name>.npy, identical for two
+    runs with the same arguments; past the size limit an array is replaced by a fixed, seeded sample.  Float64 test engine."""
+    import numpy as np
+    for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.dirname(os.path.abspath(__file__))):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import bench
+    import dib_oracle as orc
+    from _helpers import spec_kwargs
+    from _oracle_engine import OracleEngine
+
+    def run(out_dir):
+        F, gb = 8, 24
+        spec = orc.DIBSpec([1] * F, [8], [8], 1, feature_embedding_dimension=4)
+        wl = bench.Workload(F, "cpu", 0, 1, None, "strong", gb, 3, engine=OracleEngine(**spec_kwargs(spec), init_seed=0),
+                            n_rows=4 * gb)
+        wl.measure(1, 2, 2, "cpu")
+        return wl, bench.dump_outputs(wl, str(out_dir))
+
+    wl, info = run(tmp_path / "a")
+    assert set(info) == {"params", "grads", "step_out", "metrics"} and not any(v[2] for v in info.values())
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in info}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["params"], wl.eng.get_flat_params()) and got["params"].size == wl.eng.n_params
+    assert got["grads"].size == wl.eng.n_params and np.abs(got["grads"]).max() > 0
+    assert got["step_out"].shape == (wl.F + 3,) and got["metrics"].shape == (wl.F + 3,)
+    _, info_b = run(tmp_path / "b")
+    for k in info:
+        assert np.array_equal(got[k], np.load(tmp_path / "b" / f"{k}.npy")), k
+    # over the limit: the largest array is sampled down to what is left of the budget, the same elements every run
+    small = 8 * (2 * (wl.F + 3) + wl.eng.n_params + 10)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", small)
+    _, info_c = run(tmp_path / "c")
+    _, _ = run(tmp_path / "d")
+    sampled = [k for k, v in info_c.items() if v[2]]
+    assert len(sampled) == 1 and sum(np.load(tmp_path / "c" / f"{k}.npy").nbytes for k in info_c) <= small
+    k = sampled[0]
+    assert np.array_equal(np.load(tmp_path / "c" / f"{k}.npy"), np.load(tmp_path / "d" / f"{k}.npy"))
+    assert np.isin(np.load(tmp_path / "c" / f"{k}.npy"), got[k]).all()

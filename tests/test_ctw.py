@@ -19,8 +19,8 @@ from dib_amd import ctw  # noqa: E402
 import ctw_oracle  # noqa: E402
 
 
-def _golden():
-    g = np.load(os.path.join(ROOT, "tests", "golden", "ctw_golden.npz"))
+def _golden(name="ctw_golden.npz"):
+    g = np.load(os.path.join(ROOT, "tests", "golden", name))
     off = g["offsets"]
     return [(g["symbols"][off[i]:off[i + 1]], int(g["alphabet"][i]), float(g["rate"][i])) for i in range(len(off) - 1)]
 
@@ -128,27 +128,22 @@ def test_abi_exports_every_declared_symbol():
 
 
 def test_against_live_reference_build_when_present():
-    """oracle/_ref/libctw_ref.so = the reference's cppctw.cpp compiled where it lies (oracle/Makefile)."""
+    """40 random / periodic / skewed sequences against the rates the reference's cppctw.cpp gave for them
+    (tests/golden/ctw_random_cases.npz, tests/golden/make_golden_ctw.py) and, when oracle/_ref/libctw_ref.so (the reference
+    compiled where it lies, oracle/Makefile) is present, against that build live as well."""
+    cases = _golden("ctw_random_cases.npz")
+    assert len(cases) == 40
+    for seq, alphabet, rate in cases:
+        assert _same(ctw.estimate_entropy(seq, alphabet), rate), (alphabet, len(seq))
     path = os.path.join(ROOT, "oracle", "_ref", "libctw_ref.so")
     if not os.path.exists(path):
-        pytest.skip("reference build not present (no /root/reference on this machine)")
+        return
     ref = ctypes.CDLL(path)
     ref.ref_ctw_estimate_entropy.restype = ctypes.c_double
     ref.ref_ctw_estimate_entropy.argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_int]
-    rng = np.random.default_rng(77)
-    for _ in range(40):
-        a = int(rng.integers(1, 20))
-        n = int(rng.integers(1, 30000))
-        kind = rng.integers(0, 3)
-        if kind == 0:
-            s = rng.integers(0, a, n)
-        elif kind == 1:
-            s = np.tile(rng.integers(0, a, int(rng.integers(1, 50))), n // 10 + 1)[:n]      # periodic
-        else:
-            s = np.minimum((rng.random(n) ** 3 * a).astype(int), a - 1)                     # skewed
-        s8 = np.ascontiguousarray(s, dtype=np.int8)
-        want = ref.ref_ctw_estimate_entropy(s8.ctypes.data, s8.size, a)
-        assert _same(ctw.estimate_entropy(s, a), want), (a, n, kind)
+    for seq, alphabet, rate in cases:
+        s8 = np.ascontiguousarray(seq, dtype=np.int8)
+        assert _same(ref.ref_ctw_estimate_entropy(s8.ctypes.data, s8.size, alphabet), rate), (alphabet, len(seq))
 
 
 def test_chaos_data_generators_and_entropy_rate_kat():
