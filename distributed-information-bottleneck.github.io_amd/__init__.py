@@ -8,7 +8,8 @@ from . import chaos_data, ctw, data, dense, infonce, losses, models, optimizers,
 from .models import (Callback, DistributedIBNet, History, InfoBottleneckAnnealingCallback, InfoPerFeatureCallback,  # noqa: F401
                      PositionalEncoding, SaveCompressionMatricesCallback)
 from .set_transformer import SetTransformerDIB  # noqa: F401
+from .measurement import MeasurementIB  # noqa: F401
 
 __all__ = ["DistributedIBNet", "InfoBottleneckAnnealingCallback", "SaveCompressionMatricesCallback",
            "InfoPerFeatureCallback", "PositionalEncoding", "Callback", "History", "models", "losses", "optimizers", "data", "utils",
-           "visualization", "ctw", "chaos_data", "set_transformer", "SetTransformerDIB"]
+           "visualization", "ctw", "chaos_data", "set_transformer", "SetTransformerDIB", "measurement", "MeasurementIB"]

@@ -20,12 +20,13 @@ LIB_PATH = os.path.join(_HERE, "libdib_hip.so")
 LIB_OVERRIDE = os.environ.get("DIB_LIB_PATH") or None
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include", "dib_hip.h")
 INCLUDE_ST = os.path.join(os.path.dirname(_HERE), "include", "dib_st.h")
+INCLUDE_MEASURE = os.path.join(os.path.dirname(_HERE), "include", "dib_measure.h")
 SOURCES = ["dib_api.hip", "dib_gemm.h", "dib_elementwise.h", "dib_common.h", "dib_fused.h", "dib_tail.h", "dib_small.h", "dib_st_chain.h", "dib_st.h", "dib_attn.h", "dib_attn_small.h", "dib_infonce_mfma.h",
-           INCLUDE_ST]
+           "dib_measure.h", INCLUDE_ST, INCLUDE_MEASURE]
 
 # error codes (include/dib_hip.h)
 DIB_OK = 0
-ABI_VERSION = 6   # include/dib_hip.h DIB_ABI_VERSION this binding's SIGNATURES were written against
+ABI_VERSION = 7   # include/dib_hip.h DIB_ABI_VERSION this binding's SIGNATURES were written against
 ACTIVATIONS = {None: 0, "linear": 0, "None": 0, "relu": 1, "leaky_relu": 2, "tanh": 3, "sigmoid": 4, "elu": 5,
                "softplus": 6}
 ACT_LEAKY_RELU_01 = 7  # tf.keras.layers.LeakyReLU(0.1) (include/dib_st.h)
@@ -205,6 +206,18 @@ SIGNATURES_ST = {
                               c_void_p]),
 }
 
+# include/dib_measure.h: the chaos notebook's measurement-partition model
+SIGNATURES_MEASURE = {
+    "dib_measure_supported": (c_int, [c_void_p]),
+    "dib_measure_workspace_bytes": (c_int64, [c_void_p, c_int]),
+    "dib_measure_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_uint64, c_uint32, c_float, c_float, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dib_measure_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dib_measure_symbolize": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "dib_measure_posenc_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+}
+
 
 def load_library(build_if_missing: bool = True):
     """dlopen libdib_hip.so and attach signatures.  Raises (no fallback) if it cannot be loaded."""
@@ -240,7 +253,7 @@ def _attach(lib):
     if have != ABI_VERSION:
         raise RuntimeError(f"libdib_hip ABI version {have} != {ABI_VERSION} expected by this binding ({getattr(lib, '_name', '?')}): "
                            "rebuild it (python -c 'import __graft_entry__ as g; g.build()' / tools/build_variant.sh)")
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_ST.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_ST.items()) + list(SIGNATURES_MEASURE.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -65,6 +65,8 @@ def estimate_mi_sandwich_bounds(encoder, dataset, evaluation_batch_size=1024, nu
     n = x.shape[0]
     bs = int(evaluation_batch_size)
     rng = np.random.default_rng(seed)
+    if getattr(encoder, "_encoder", False):   # MeasurementIB.info_bott_encoder (chaos notebook cell 10): its [N, 2E] output
+        return _measurement_mi_bounds(encoder, x, n, bs, rng, int(number_evaluation_batches), seed)
     model = encoder._model
     eng = model._ensure_engine()
     estimates = []
@@ -72,4 +74,25 @@ def estimate_mi_sandwich_bounds(encoder, dataset, evaluation_batch_size=1024, nu
         rows = rng.permutation(n)[:bs] if n >= bs else rng.integers(0, n, bs)
         enc_out = eng.encode_feature(encoder.index, x[rows])
         estimates.append(eng.mi_sandwich_bounds(enc_out, seed, b, encoder.index))
+    return np.mean(np.stack(estimates, 0), 0)
+
+
+def _measurement_mi_bounds(encoder, x, n, bs, rng, number_evaluation_batches, seed):
+    import ctypes
+
+    import torch
+
+    from ._gemm_plan import _ptr
+    from ._lib import check
+    m = encoder._measurement
+    estimates = []
+    for b in range(number_evaluation_batches):
+        rows = rng.permutation(n)[:bs] if n >= bs else rng.integers(0, n, bs)
+        enc_out = encoder(x[rows])
+        e = enc_out.shape[1] // 2
+        ws = torch.empty(int(m.lib.dib_mi_workspace_bytes(bs, e)) // 8 + 1, dtype=torch.float64, device=m.device)
+        r = torch.empty((2, bs), dtype=torch.float64, device=m.device)
+        check(m.lib.dib_mi_sandwich_rows(_ptr(enc_out), bs, e, int(seed), b & 0xFFFFFFFF, 0, _ptr(r[0]), _ptr(r[1]), _ptr(ws),
+                                         ctypes.c_void_p(torch.cuda.current_stream(m.device).cuda_stream)), "dib_mi_sandwich_rows")
+        estimates.append(r.mean(dim=1).cpu().numpy())
     return np.mean(np.stack(estimates, 0), 0)

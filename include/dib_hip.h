@@ -92,8 +92,8 @@ const char* dib_version(void);
  * experimental bf16x6 GEMM entry points left the library); 6 = round 6 (dib_st_chain_bwd takes its incoming
  * gradient as g_out_slabs partial buffers; dib_mlp_small_head_{supported,workspace_bytes,step} and dib_attention_fwd_proj{,_supported}, dib_attention_bwd_proj added; dib_mlp_desc.act accepts
  * DIB_ACT_LEAKY_RELU_01; the tuning key "num_cus" = 0 now means "the calling thread's current device's own
- * count" and the library no longer writes it). */
-#define DIB_ABI_VERSION 6
+ * count" and the library no longer writes it); 7 = the measurement-partition entry points of dib_measure.h). */
+#define DIB_ABI_VERSION 7
 int dib_abi_version(void);
 const char* dib_error_string(int code);
 
