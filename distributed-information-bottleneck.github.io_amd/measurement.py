@@ -100,12 +100,18 @@ class MeasurementIB:
                  reference_state_encoder_arch_spec=(256, 256), reference_timestep: int = 0, infonce_embedding_dimension: int = 32,
                  infonce_similarity: str = "l2sq", infonce_temperature: float = 1., activation_function: str = "leaky_relu",
                  noise_seed: int = 0, init_seed: int = 0, device="cuda:0"):
+        # the reference state is states_batch[:, reference_timestep] (NumPy indexing: -1 is the last state); any other value
+        # would read a state of the next sequence, or past the trajectory
+        L = int(number_states)
+        if not -L <= int(reference_timestep) < L:
+            raise ValueError(f"reference_timestep {reference_timestep} outside the sequence: -{L} <= reference_timestep < {L}")
+        reference_timestep = int(reference_timestep) % L
         if not torch.cuda.is_available():
             raise RuntimeError("MeasurementIB runs on the GPU (libdib_hip); no device is available")
         self.d, self.L, self.A = int(input_dimensionality), int(number_states), int(alphabet_size)
         self.E, self.p = int(information_bottleneck_embedding_dimension), float(kl_loss_exponent)
         self.n_freq = int(number_positional_encoding_frequencies) + 1   # x and its sines
-        self.reference_timestep, self.D = int(reference_timestep), int(infonce_embedding_dimension)
+        self.reference_timestep, self.D = reference_timestep, int(infonce_embedding_dimension)
         self.similarity, self.temperature = SIMILARITIES[infonce_similarity], float(infonce_temperature)
         self.noise_seed = int(noise_seed)
         self.eng = _Eng(device)

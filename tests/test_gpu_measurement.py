@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import _oracle_measurement as om
+from _helpers import dispatch_path
 from dib_amd import chaos_data
 from dib_amd.measurement import MeasurementIB
 
@@ -46,6 +47,31 @@ CONFIGS = {
                                                        measurement_aggregator_arch_spec=(64, 64),
                                                        reference_state_encoder_arch_spec=(48, 48), kl_loss_exponent=1.5), p=1.5),
 }
+# the kernels' envelope and the loss options, one short step each (from the ragged_p1.5 shapes)
+_SMALL = dict(CONFIGS["ragged_p1.5"]["kw"], kl_loss_exponent=2.0)
+for _name, _b, _kw in [("relu", 96, dict(activation_function="relu")),
+                       ("linear", 96, dict(activation_function="linear")),
+                       ("e17", 96, dict(information_bottleneck_embedding_dimension=17)),
+                       ("e32", 96, dict(information_bottleneck_embedding_dimension=32)),
+                       ("a5", 96, dict(alphabet_size=5)),
+                       ("a16", 96, dict(alphabet_size=16)),
+                       ("l1", 96, dict(number_states=1)),
+                       ("l32", 96, dict(number_states=32)),
+                       ("d3", 96, dict(input_dimensionality=3)),
+                       ("d4", 96, dict(input_dimensionality=4)),
+                       ("ragged_rows259", 37, dict(number_states=7)),
+                       ("reference_last", 96, dict(reference_timestep=4)),
+                       ("reference_minus1", 96, dict(reference_timestep=-1)),
+                       ("temperature0.5", 96, dict(infonce_temperature=0.5)),
+                       ("cosine", 96, dict(infonce_similarity="cosine")),
+                       # 2E = 16 and B L = 480 <= 2048: the IB encoder on the row-tile kernel (dib_mlp_small_fwd, gathered rows)
+                       ("ib_row_tiles_e8", 96, dict(information_bottleneck_embedding_dimension=8))]:
+    CONFIGS[_name] = dict(traj="uniform", B=_b, kw=dict(_SMALL, **_kw), p=2.0)
+
+
+def _oracle_options(kw):
+    return dict(reference_timestep=kw.get("reference_timestep", 0), temperature=kw.get("infonce_temperature", 1.0),
+                similarity=kw.get("infonce_similarity", "l2sq"), slope=om.SLOPES[kw.get("activation_function", "leaky_relu")])
 
 
 def _traj(kind, n, d):
@@ -54,20 +80,25 @@ def _traj(kind, n, d):
     return np.random.default_rng(3).uniform(-1, 1, (n, d)).astype(np.float32)
 
 
-@pytest.mark.parametrize("name", list(CONFIGS))
-def test_step_losses_and_all_gradients_match_oracle(name):
+# both sides of the DenseStack switch (tests/_helpers.py DISPATCH_PATHS): "default" takes the row-tile kernels for batches of
+# <= 2048 rows whose layer widths are multiples of 16, "large_batch" the grouped GEMMs everywhere; dib_measure_bwd reads the
+# aggregator's g1 from whichever ran
+@pytest.mark.parametrize("name,path", [pytest.param(n, p, id=n if p == "default" else f"{n}-{p}")
+                                       for p in ("default", "large_batch") for n in CONFIGS])
+def test_step_losses_and_all_gradients_match_oracle(name, path):
     c = CONFIGS[name]
-    m = MeasurementIB(**c["kw"], noise_seed=11, init_seed=5)
+    with dispatch_path(path):
+        m = MeasurementIB(**c["kw"], noise_seed=11, init_seed=5)
+        loss, lp, kl, w, states, beta = _one_step(m, c)
+        # which kernels ran: the VQ chain always in dib_measure_fwd; the other three networks on DenseStack
+        assert m.vq._last is None
+        for s, n in [(m.ib, c["B"] * m.L), (m.agg, c["B"]), (m.ref, c["B"])]:
+            want = path == "default" and n <= 2048 and all(o % 16 == 0 for _, o in s.dims)
+            assert s._last["small"] == want, (path, s.dims, n, s._last["small"])
     L, d, B, E = m.L, m.d, c["B"], m.E
-    traj = _traj(c["traj"], 20_000, d)
-    starts = np.random.default_rng(1).choice(len(traj) - L, size=B)
-    states = traj[om_idx(starts, L)]
-    w = _weights(m)
-    beta = 0.37
-    m.beta = beta
-    loss, lp, kl = m.match_batch(states, training=True)
     eps = om.eps_rows(11, 0, np.arange(B * L), E)
-    rl, rlp, rkl, rg = om.match_batch(w, states.astype(np.float64), eps, np.float32(beta), c["p"], m.n_freq)
+    rl, rlp, rkl, rg = om.match_batch(w, states.astype(np.float64), eps, np.float32(beta), c["p"], m.n_freq,
+                                      **_oracle_options(c["kw"]))
     assert abs(kl - rkl) <= 1e-5 * abs(rkl), (kl, rkl)
     assert abs(lp - rlp) <= 1e-5 * abs(rlp), (lp, rlp)
     assert abs(loss - rl) <= 1e-5 * abs(rl), (loss, rl)
@@ -75,6 +106,40 @@ def test_step_losses_and_all_gradients_match_oracle(name):
     for net in rg:
         for i, (a, b) in enumerate(zip(g[net], rg[net])):
             assert _rel(a, b) <= 1e-4, (net, i, _rel(a, b))
+
+
+def test_config_grid_reaches_the_row_tile_ib_encoder():
+    """at least one config puts the IB encoder on the row-tile kernel by default (2E % 16 == 0, B L <= 2048)"""
+    assert any(2 * c["kw"].get("information_bottleneck_embedding_dimension", 8) % 16 == 0
+               and c["B"] * c["kw"].get("number_states", 12) <= 2048 for c in CONFIGS.values())
+
+
+def _one_step(m, c):
+    """one training step of config c on model m: (loss, loss_prediction, kl, the weights before it, states, beta)"""
+    L, d, B = m.L, m.d, c["B"]
+    traj = _traj(c["traj"], 20_000, d)
+    starts = np.random.default_rng(1).choice(len(traj) - L, size=B)
+    states = traj[om_idx(starts, L)]
+    w = _weights(m)
+    beta = 0.37
+    m.beta = beta
+    loss, lp, kl = m.match_batch(states, training=True)
+    return loss, lp, kl, w, states, beta
+
+
+def test_reference_timestep_minus_one_is_the_last_state():
+    """NumPy indexing: reference_timestep = -1 is stored as L - 1 and gives the same bits as L - 1"""
+    c = CONFIGS["reference_last"]
+    out = []
+    for r in (-1, 4):
+        m = MeasurementIB(**dict(c["kw"], reference_timestep=r), noise_seed=11, init_seed=5)
+        assert m.reference_timestep == m.L - 1
+        loss, lp, kl, _, _, _ = _one_step(m, c)
+        out.append(((loss, lp, kl), _grads(m)))
+    assert out[0][0] == out[1][0], out
+    for net in out[0][1]:
+        for a, b in zip(out[0][1][net], out[1][1][net]):
+            assert np.array_equal(a, b), net
 
 
 def om_idx(starts, L):
@@ -137,6 +202,27 @@ def test_symbolize_matches_oracle(trained):
     assert np.array_equal(sym[~near], ref[~near])
     assert counts.sum(1).tolist() == [100] * len(x)
     m.vector_quantization_network.set_weights(vw)
+
+
+def test_symbolize_a5_symbols_and_counts_match_oracle():
+    """A = 5: logits in two lane groups, symbols >= 4 in the counts, the mean-argmax rule (not a vote) in sym"""
+    m = MeasurementIB(2, alphabet_size=5, information_bottleneck_embedding_dimension=17, noise_seed=0, init_seed=3)
+    x = _ikeda(3000, seed=2)
+    noise = np.random.default_rng(8).standard_normal((100, m.E)).astype(np.float32)
+    sym, counts = m.symbolize(x, noise_vector=noise, return_counts=True)
+    enc = om.encode(m.info_bott_encoder.get_weights(), x, m.n_freq)
+    lg = om.vq_logits(m.vector_quantization_network.get_weights(), enc[:, :m.E], enc[:, m.E:], noise)
+    am = np.argmax(lg, -1)
+    top2 = np.sort(lg, -1)[..., -2:]
+    # an untrained partition: near-ties (top two within 1e-5 of the draw's largest |logit|, where the fp32 encoder and the
+    # fp64 oracle may disagree) exclude a few points in a thousand
+    near = np.any(top2[..., 1] - top2[..., 0] < 1e-5 * np.abs(lg).max(-1), axis=0)
+    assert near.mean() <= 1e-2, (near.mean(), "near-tie exclusions above 1 %")
+    ref_counts = np.stack([(am == a).sum(0) for a in range(5)], 1)
+    assert np.array_equal(counts[~near], ref_counts[~near])
+    assert np.array_equal(sym[~near], np.uint8(np.mean(am, 0) > 0.5)[~near])
+    assert counts.sum(1).tolist() == [100] * len(x)
+    assert counts[:, 4].any() and counts[:, 0].any(), "symbols of both lane groups are drawn"
 
 
 def test_symbolize_is_bit_identical_across_runs_chunks_and_noise_source(trained):

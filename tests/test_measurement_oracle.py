@@ -39,6 +39,67 @@ def test_oracle_gradients_agree_with_central_differences(p):
                 assert abs(fd - g[net][i][idx]) <= 1e-6 * max(1.0, abs(fd)), (net, i, idx, fd, g[net][i][idx])
 
 
+def _central_difference_check(w, f, g, rng, h=1e-6, per_array=3):
+    for net in w:
+        for i, arr in enumerate(w[net]):
+            for idx in [tuple(rng.integers(0, s) for s in arr.shape) for _ in range(per_array)]:
+                wp = {k: [a.copy() for a in v] for k, v in w.items()}
+                wm = {k: [a.copy() for a in v] for k, v in w.items()}
+                wp[net][i][idx] += h
+                wm[net][i][idx] -= h
+                fd = (f(wp) - f(wm)) / (2 * h)
+                assert abs(fd - g[net][i][idx]) <= 1e-6 * max(1.0, abs(fd)), (net, i, idx, fd, g[net][i][idx], "bound 1e-6")
+
+
+# the loss options the constructor accepts: similarity, temperature, reference state, hidden activation (leaky_relu 0.2,
+# relu 0, linear 1), each away from the notebook's default
+OPTIONS = {
+    "l1": dict(similarity="l1"),
+    "cosine": dict(similarity="cosine"),
+    "temperature0.5": dict(temperature=0.5),
+    "l2sq_temperature3": dict(similarity="l2sq", temperature=3.0),
+    "reference_timestep2": dict(reference_timestep=2),
+    "reference_timestep-1": dict(reference_timestep=-1),
+    "relu": dict(slope=0.0),
+    "linear": dict(slope=1.0),
+    "cosine_relu_ref1": dict(similarity="cosine", slope=0.0, reference_timestep=1, temperature=0.7),
+}
+
+
+@pytest.mark.parametrize("name", list(OPTIONS))
+def test_oracle_gradients_over_the_loss_options_agree_with_central_differences(name):
+    kw = OPTIONS[name]
+    rng = np.random.default_rng(1)
+    w = _tiny(rng)
+    states = rng.uniform(-1, 1, (4, 3, 1))
+    eps = rng.standard_normal((12, 2))
+    f = lambda ww: om.match_batch(ww, states, eps, 0.7, 2.0, 3, grads=False, **kw)[0]
+    _, _, _, g = om.match_batch(w, states, eps, 0.7, 2.0, 3, **kw)
+    _central_difference_check(w, f, g, rng)
+
+
+def test_oracle_options_change_the_loss():
+    """each option reaches the loss (a parameter the restatement dropped would pass the difference check above)"""
+    rng = np.random.default_rng(1)
+    w = _tiny(rng)
+    states = rng.uniform(-1, 1, (4, 3, 1))
+    eps = rng.standard_normal((12, 2))
+    base = om.match_batch(w, states, eps, 0.7, 2.0, 3, grads=False)[0]
+    for kw in OPTIONS.values():
+        assert abs(om.match_batch(w, states, eps, 0.7, 2.0, 3, grads=False, **kw)[0] - base) > 1e-6, kw
+    # NumPy indexing: -1 is the last state of the sequence
+    last = om.match_batch(w, states, eps, 0.7, 2.0, 3, grads=False, reference_timestep=2)[0]
+    assert om.match_batch(w, states, eps, 0.7, 2.0, 3, grads=False, reference_timestep=-1)[0] == last
+
+
+@pytest.mark.parametrize("ref", [3, 4, 100, -4, -5])
+def test_reference_timestep_outside_the_sequence_is_refused(ref):
+    """states_batch[:, reference_timestep] for L = 3 accepts -3 .. 2; anything else read a state of the next sequence or past
+    the trajectory.  Validated before the device check, so this runs without a GPU."""
+    with pytest.raises(ValueError, match="reference_timestep"):
+        measurement.MeasurementIB(1, number_states=3, reference_timestep=ref)
+
+
 def test_beta_schedule_is_the_notebook_formula():
     for step, n in [(0, 20_000), (1, 20_000), (9_999, 20_000), (19_999, 20_000), (25_000, 20_000), (3, 30)]:
         want = np.exp(np.log(10) + min(float(step) / n, 1.) * (np.log(1e-4) - np.log(10)))
