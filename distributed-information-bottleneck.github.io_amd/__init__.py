@@ -9,7 +9,10 @@ from .models import (Callback, DistributedIBNet, History, InfoBottleneckAnnealin
                      PositionalEncoding, SaveCompressionMatricesCallback)
 from .set_transformer import SetTransformerDIB  # noqa: F401
 from .measurement import MeasurementIB  # noqa: F401
+from . import circuit  # noqa: F401
+from .circuit import CircuitIB  # noqa: F401
 
 __all__ = ["DistributedIBNet", "InfoBottleneckAnnealingCallback", "SaveCompressionMatricesCallback",
            "InfoPerFeatureCallback", "PositionalEncoding", "Callback", "History", "models", "losses", "optimizers", "data", "utils",
-           "visualization", "ctw", "chaos_data", "set_transformer", "SetTransformerDIB", "measurement", "MeasurementIB"]
+           "visualization", "ctw", "chaos_data", "set_transformer", "SetTransformerDIB", "measurement", "MeasurementIB",
+           "circuit", "CircuitIB"]

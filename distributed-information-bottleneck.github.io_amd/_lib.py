@@ -21,8 +21,9 @@ LIB_OVERRIDE = os.environ.get("DIB_LIB_PATH") or None
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include", "dib_hip.h")
 INCLUDE_ST = os.path.join(os.path.dirname(_HERE), "include", "dib_st.h")
 INCLUDE_MEASURE = os.path.join(os.path.dirname(_HERE), "include", "dib_measure.h")
+INCLUDE_CIRCUIT = os.path.join(os.path.dirname(_HERE), "include", "dib_circuit.h")
 SOURCES = ["dib_api.hip", "dib_gemm.h", "dib_elementwise.h", "dib_common.h", "dib_fused.h", "dib_tail.h", "dib_small.h", "dib_st_chain.h", "dib_st.h", "dib_attn.h", "dib_attn_small.h", "dib_infonce_mfma.h",
-           "dib_measure.h", INCLUDE_ST, INCLUDE_MEASURE]
+           "dib_measure.h", "dib_circuit.h", INCLUDE_ST, INCLUDE_MEASURE, INCLUDE_CIRCUIT]
 
 # error codes (include/dib_hip.h)
 DIB_OK = 0
@@ -218,6 +219,17 @@ SIGNATURES_MEASURE = {
     "dib_measure_posenc_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 
+# include/dib_circuit.h: the Boolean-circuit notebook's scalar-channel model
+SIGNATURES_CIRCUIT = {
+    "dib_circuit_supported": (c_int, [c_int, c_int]),
+    "dib_circuit_fwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_uint64, c_uint32, c_float, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p]),
+    "dib_circuit_bwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_uint64, c_uint32, c_float, c_void_p, c_void_p, c_void_p,
+                                c_void_p]),
+    "dib_circuit_mi_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "dib_circuit_mi_bounds": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_uint64, c_void_p, c_void_p, c_void_p]),
+}
+
 
 def load_library(build_if_missing: bool = True):
     """dlopen libdib_hip.so and attach signatures.  Raises (no fallback) if it cannot be loaded."""
@@ -253,7 +265,8 @@ def _attach(lib):
     if have != ABI_VERSION:
         raise RuntimeError(f"libdib_hip ABI version {have} != {ABI_VERSION} expected by this binding ({getattr(lib, '_name', '?')}): "
                            "rebuild it (python -c 'import __graft_entry__ as g; g.build()' / tools/build_variant.sh)")
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_ST.items()) + list(SIGNATURES_MEASURE.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_ST.items()) + list(SIGNATURES_MEASURE.items()) \
+            + list(SIGNATURES_CIRCUIT.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

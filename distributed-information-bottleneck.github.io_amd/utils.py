@@ -67,6 +67,8 @@ def estimate_mi_sandwich_bounds(encoder, dataset, evaluation_batch_size=1024, nu
     rng = np.random.default_rng(seed)
     if getattr(encoder, "_encoder", False):   # MeasurementIB.info_bott_encoder (chaos notebook cell 10): its [N, 2E] output
         return _measurement_mi_bounds(encoder, x, n, bs, rng, int(number_evaluation_batches), seed)
+    if getattr(encoder, "_circuit", None) is not None:   # CircuitIB.feature_encoders[g] (Boolean-circuit notebook cell 4)
+        return _circuit_mi_bounds(encoder, x, n, bs, rng, int(number_evaluation_batches), seed)
     model = encoder._model
     eng = model._ensure_engine()
     estimates = []
@@ -93,6 +95,29 @@ def _measurement_mi_bounds(encoder, x, n, bs, rng, number_evaluation_batches, se
         ws = torch.empty(int(m.lib.dib_mi_workspace_bytes(bs, e)) // 8 + 1, dtype=torch.float64, device=m.device)
         r = torch.empty((2, bs), dtype=torch.float64, device=m.device)
         check(m.lib.dib_mi_sandwich_rows(_ptr(enc_out), bs, e, int(seed), b & 0xFFFFFFFF, 0, _ptr(r[0]), _ptr(r[1]), _ptr(ws),
+                                         ctypes.c_void_p(torch.cuda.current_stream(m.device).cuda_stream)), "dib_mi_sandwich_rows")
+        estimates.append(r.mean(dim=1).cpu().numpy())
+    return np.mean(np.stack(estimates, 0), 0)
+
+
+def _circuit_mi_bounds(encoder, x, n, bs, rng, number_evaluation_batches, seed):
+    """one gate's channel, batch by batch through dib_mi_sandwich_rows on its [bs, 2] output (noise feature = the gate index):
+    the per-gate form of CircuitIB.estimate_channel_mi_bounds' one-launch evaluation"""
+    import ctypes
+
+    import torch
+
+    from ._gemm_plan import _ptr
+    from ._lib import check
+    m = encoder._circuit
+    ws = torch.empty(int(m.lib.dib_mi_workspace_bytes(bs, 1)) // 8 + 1, dtype=torch.float64, device=m.device)
+    estimates = []
+    for b in range(number_evaluation_batches):
+        rows = rng.permutation(n)[:bs] if n >= bs else rng.integers(0, n, bs)
+        enc_out = encoder(x[rows]).contiguous()
+        r = torch.empty((2, bs), dtype=torch.float64, device=m.device)
+        check(m.lib.dib_mi_sandwich_rows(_ptr(enc_out), bs, 1, int(seed) & (2 ** 64 - 1), b & 0xFFFFFFFF, encoder.index,
+                                         _ptr(r[0]), _ptr(r[1]), _ptr(ws),
                                          ctypes.c_void_p(torch.cuda.current_stream(m.device).cuda_stream)), "dib_mi_sandwich_rows")
         estimates.append(r.mean(dim=1).cpu().numpy())
     return np.mean(np.stack(estimates, 0), 0)
