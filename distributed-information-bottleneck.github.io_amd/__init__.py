@@ -11,8 +11,10 @@ from .set_transformer import SetTransformerDIB  # noqa: F401
 from .measurement import MeasurementIB  # noqa: F401
 from . import circuit  # noqa: F401
 from .circuit import CircuitIB  # noqa: F401
+from . import random_partition  # noqa: F401
+from .random_partition import RandomPartition  # noqa: F401
 
 __all__ = ["DistributedIBNet", "InfoBottleneckAnnealingCallback", "SaveCompressionMatricesCallback",
            "InfoPerFeatureCallback", "PositionalEncoding", "Callback", "History", "models", "losses", "optimizers", "data", "utils",
            "visualization", "ctw", "chaos_data", "set_transformer", "SetTransformerDIB", "measurement", "MeasurementIB",
-           "circuit", "CircuitIB"]
+           "circuit", "CircuitIB", "random_partition", "RandomPartition"]

@@ -22,8 +22,9 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), "include", "dib_hip.h")
 INCLUDE_ST = os.path.join(os.path.dirname(_HERE), "include", "dib_st.h")
 INCLUDE_MEASURE = os.path.join(os.path.dirname(_HERE), "include", "dib_measure.h")
 INCLUDE_CIRCUIT = os.path.join(os.path.dirname(_HERE), "include", "dib_circuit.h")
+INCLUDE_PARTITION = os.path.join(os.path.dirname(_HERE), "include", "dib_partition.h")
 SOURCES = ["dib_api.hip", "dib_gemm.h", "dib_elementwise.h", "dib_common.h", "dib_fused.h", "dib_tail.h", "dib_small.h", "dib_st_chain.h", "dib_st.h", "dib_attn.h", "dib_attn_small.h", "dib_infonce_mfma.h",
-           "dib_measure.h", "dib_circuit.h", INCLUDE_ST, INCLUDE_MEASURE, INCLUDE_CIRCUIT]
+           "dib_measure.h", "dib_circuit.h", "dib_partition.h", INCLUDE_ST, INCLUDE_MEASURE, INCLUDE_CIRCUIT, INCLUDE_PARTITION]
 
 # error codes (include/dib_hip.h)
 DIB_OK = 0
@@ -230,6 +231,13 @@ SIGNATURES_CIRCUIT = {
     "dib_circuit_mi_bounds": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_uint64, c_void_p, c_void_p, c_void_p]),
 }
 
+# include/dib_partition.h: the chaos notebook's random-MLP partitions
+SIGNATURES_PARTITION = {
+    "dib_partition_supported": (c_int, [c_void_p]),
+    "dib_partition_symbolize": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                        c_void_p]),
+}
+
 
 def load_library(build_if_missing: bool = True):
     """dlopen libdib_hip.so and attach signatures.  Raises (no fallback) if it cannot be loaded."""
@@ -266,7 +274,7 @@ def _attach(lib):
         raise RuntimeError(f"libdib_hip ABI version {have} != {ABI_VERSION} expected by this binding ({getattr(lib, '_name', '?')}): "
                            "rebuild it (python -c 'import __graft_entry__ as g; g.build()' / tools/build_variant.sh)")
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_ST.items()) + list(SIGNATURES_MEASURE.items()) \
-            + list(SIGNATURES_CIRCUIT.items()):
+            + list(SIGNATURES_CIRCUIT.items()) + list(SIGNATURES_PARTITION.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

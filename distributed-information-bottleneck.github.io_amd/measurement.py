@@ -306,10 +306,10 @@ class MeasurementIB:
         return self.info_bott_encoder(x)
 
 
-def characterize_partition(symbolic_sequence, alphabet_size: int, number_data_points=None, number_rand_draws: int = 5,
-                           seed: int = 0) -> dict:
-    """cell 10 after the symbolisation: H(U) of one symbol, CTW entropy rates of `number_rand_draws` random windows of each
-    length (15 log-spaced lengths 2e3 .. 2e6 by default) and the Schurmann-Grassberger fit h(N) = h + log2 N / N^g / |c|."""
+def entropy_rate_fit(symbolic_sequence, alphabet_size: int, number_data_points=None, number_rand_draws: int = 5, seed: int = 0,
+                     threads: int = 0) -> dict:
+    """CTW entropy rates of `number_rand_draws` random windows of each length (15 log-spaced lengths 2e3 .. 2e6 by default),
+    on `threads` host threads (0 = all), and the Schurmann-Grassberger fit h(N) = h + log2 N / N^g / |c|."""
     from scipy import optimize
     seq = np.asarray(symbolic_sequence)
     if number_data_points is None:
@@ -321,8 +321,18 @@ def characterize_partition(symbolic_sequence, alphabet_size: int, number_data_po
         for _ in range(number_rand_draws):
             s = rng.choice(len(seq) - int(n))
             windows.append(seq[s: s + int(n)])
-    rates = np.asarray(ctw.estimate_entropy_batch(windows, alphabet_size), dtype=np.float64).reshape(-1, number_rand_draws)
+    rates = np.asarray(ctw.estimate_entropy_batch(windows, alphabet_size, threads=threads),
+                       dtype=np.float64).reshape(-1, number_rand_draws)
     mean, err = rates.mean(1), rates.std(1)
     fit_vals, pcov = optimize.curve_fit(utils.entropy_rate_scaling_ansatz, number_data_points, mean, p0=[1, 0.5, 1], sigma=err)
-    return {"entropy_single_timestep": float(utils.compute_entropy(seq)), "number_data_points": number_data_points,
-            "entropy_rate_values": rates, "entropy_rate": float(fit_vals[0]), "entropy_rate_err": float(np.sqrt(np.diag(pcov))[0])}
+    return {"number_data_points": number_data_points, "entropy_rate_values": rates, "entropy_rate": float(fit_vals[0]),
+            "entropy_rate_err": float(np.sqrt(np.diag(pcov))[0])}
+
+
+def characterize_partition(symbolic_sequence, alphabet_size: int, number_data_points=None, number_rand_draws: int = 5,
+                           seed: int = 0, threads: Optional[int] = None) -> dict:
+    """cell 10 after the symbolisation: H(U) of one symbol and entropy_rate_fit of the sequence.  threads: CTW host threads
+    (None or 0 = all hardware threads)."""
+    seq = np.asarray(symbolic_sequence)
+    fit = entropy_rate_fit(seq, alphabet_size, number_data_points, number_rand_draws, seed, threads=int(threads or 0))
+    return {"entropy_single_timestep": float(utils.compute_entropy(seq)), **fit}

@@ -54,6 +54,9 @@ ORACLE_TESTS = {
     "test_gpu_circuit.py": {
         "test_drawn_rows_eps_and_u_match_oracle", "test_step_bce_kl_and_all_gradients_match_oracle",
         "test_thirty_adam_steps_through_the_beta_ramp_match_oracle", "test_mi_bounds_match_compute_batch_and_the_per_gate_loop"},
+    "test_gpu_random_partition.py": {
+        "test_kernel_matches_oracle_across_the_envelope", "test_duplicated_and_negated_columns_go_to_the_lower_index",
+        "test_notebook_configurations_match_the_oracle", "test_logistic_generating_partition_known_answer"},
     "test_gpu_building_blocks.py": {
         "test_softmax_rows_forward_backward_vs_float64", "test_add_layernorm_forward_backward_vs_float64", "test_act_grad_mul_vs_numpy",
         "test_sgd_step_vs_numpy", "test_gemm_tile_shapes_the_default_rules_rarely_pick", "test_weight_gradient_flat_tile_vs_numpy", "test_attention_forward_with_projections_vs_float64", "test_attention_backward_with_projection_gradient_vs_float64"},
