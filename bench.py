@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py - headline benchmark of the MI355X-native Distributed-IB training path.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: set up, W warm-up steps, the timed blocks, `--dump-outputs` if given, and
+the result line.  Everything else it can measure - the per-kernel timing block (`roofline` of the dominant kernel), the
+`extra` measurements and the `cpu_baseline` - runs only under `--full` (see below); `--no-kernel-timing`, `--no-extra` and
+`--no-cpu-baseline` leave single parts of that out.  Without the kernel-timing block, `roofline` is the whole-step figure.
 
 `--gpus N` with N > 1 and no launcher environment: bench.py re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`, one rank per GPU, RCCL
@@ -15,22 +20,24 @@ resident in HBM, global batch 65536 (16 distinct batches), architecture = the re
 fp32 end to end like the reference.
 
 Scaling: default STRONG - the 65536-row global batch is sharded, rank r takes rows [r*B/N, (r+1)*B/N) of
-each global batch; `--scaling weak` keeps 65536 rows per GPU.  With N > 1 the other mode is measured too and reported
-under `extra`.
+each global batch; `--scaling weak` keeps 65536 rows per GPU.  With N > 1 and `--full` the other mode is measured too and
+reported under `extra`.
 
 Timing: W warm-up steps, then `--blocks` (default 3) timed blocks of EXACTLY K steps, each bracketed by barrier +
 torch.cuda.synchronize() on both sides, max over ranks; `value` is the MEDIAN block (box-to-box and run-to-run spread is
-6-8 %, so a single block is noisy); all blocks are listed.  These blocks run WITHOUT per-kernel event timing.  One more
-K-step block then runs with HIP events around every MFMA kernel (inside libdib_hip.so, on the launch stream) for the
-`roofline` of the dominant kernel; its step time is reported as `ms_per_step_kernel_timing`.
+6-8 %, so a single block is noisy); all blocks are listed.  These blocks run WITHOUT per-kernel event timing.  With `--full`
+one more K-step block then runs with HIP events around every MFMA kernel (inside libdib_hip.so, on the launch stream) for
+the `roofline` of the dominant kernel; its step time is reported as `ms_per_step_kernel_timing`.
 
 `--dump-outputs DIR`: after the timed blocks (before the kernel-timing block and any `extra`), rank 0 writes what the headline
 step computed in its last step as DIR/<name>.npy (see dump_outputs); the inputs are fixed (seeded data, init_seed=0,
 noise seed 0), so two builds run with the same arguments can be compared output for output.
 
-One JSON line on rank 0 with `roofline`, `cpu_baseline` (PyTorch-CPU eager restatement of the TF graph,
+One JSON line on rank 0 with `roofline`; under `--full` also `cpu_baseline` (PyTorch-CPU eager restatement of the TF graph,
 oracle/dib_torch_cpu.py, timed on this box's host cores on a bounded sample; N=1 only) and `extra` (BASELINE config 4,
-F = 50 shell features, same step at B = 65536; N=1 only).
+F = 50 shell features, same step at B = 65536; the fit surface, config 5, the notebook-size set transformer, the reference's
+default batch and the config-2 loop; N=1 only; N > 1: the data-parallel breakdown, the other scaling mode and config 5 over
+neighbourhoods).
 """
 import argparse
 import json
@@ -669,10 +676,9 @@ class _ExtrasDeadline:
         self.timer.cancel()
 
 
-def main():
-    if len(sys.argv) >= 4 and sys.argv[1] == "--cpu-baseline-worker":
-        _cpu_baseline_worker(int(sys.argv[2]), float(sys.argv[3]))
-        return 0
+def parse_args(argv=None):
+    """The command line, with `--full` resolved: without it the kernel-timing block, every `extra` and the CPU baseline are
+    off (args.no_kernel_timing = args.no_extra = args.no_cpu_baseline = True); `--force-dp-extras` implies `--full`."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -684,12 +690,16 @@ def main():
     ap.add_argument("--features", type=int, default=64,
                     help="number of scalar features of the synthetic workload: 64 = BASELINE config 3 (the headline), 50 = "
                          "BASELINE config 4 (what the rocprofv3 passes of profiles/*_config4_* wrap)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the `extra` measurements (other scaling mode, config 4)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the per-kernel timing block (`roofline` of the dominant "
+                         "kernel), the `extra` measurements and the CPU baseline; a plain run times the steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the `extra` measurements (other scaling mode, config 4, ...)")
     ap.add_argument("--dp-buckets", type=int, default=3, choices=[1, 2, 3],
                     help="gradient all-reduce buckets: 3 (default) = integration / encoder front layers / last encoder layer, each "
                          "issued as soon as it is final; 2 = integration overlapped, whole encoder bank after the backward; 1 = one")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the per-kernel timing block")
     ap.add_argument("--extra-timeout", type=float, default=240.0,
                     help="N > 1: seconds the `extra` measurements may take before the headline line is printed without them")
     ap.add_argument("--config5-only", action="store_true",
@@ -700,14 +710,26 @@ def main():
     ap.add_argument("--force-dp-extras", action="store_true",
                     help="run the multi-GPU `extra` measurements (dp_breakdown, other scaling mode) under ONE RCCL rank too "
                          "(python -m torch.distributed.run --nproc-per-node 1 bench.py --gpus 1 --force-dp-extras): exercises the code "
-                         "path the driver's SCALE run takes")
+                         "path the driver's SCALE run takes; implies --full")
     ap.add_argument("--only-dp-breakdown", action="store_true",
                     help="with --force-dp-extras: the data-parallel breakdown is the only extra (the per-GPU operating point, "
                          "e.g. --batch 8192 under one RCCL rank)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed blocks, write what the last timed step computed as DIR/<name>.npy (bench.dump_outputs)")
     ap.add_argument("--dry-run-backend", default=None, help=argparse.SUPPRESS)  # CPU test of the launcher path (gloo)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.force_dp_extras:
+        args.full = True
+    if not args.full:
+        args.no_kernel_timing = args.no_extra = args.no_cpu_baseline = True
+    return args
+
+
+def main():
+    if len(sys.argv) >= 4 and sys.argv[1] == "--cpu-baseline-worker":
+        _cpu_baseline_worker(int(sys.argv[2]), float(sys.argv[3]))
+        return 0
+    args = parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ:
         return _respawn_under_launcher(args.gpus)

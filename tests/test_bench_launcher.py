@@ -37,6 +37,23 @@ def test_flop_model_matches_survey():
     assert sum(bench.flops_by_kernel().values()) == 13141504
 
 
+def test_plain_run_measures_the_headline_only_and_full_restores_the_rest():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` runs no kernel-timing block, no `extra` and no CPU baseline; `--full`
+    turns all three back on, the `--no-*` switches still leave single parts out, and `--force-dp-extras` implies `--full`."""
+    sys.path.insert(0, ROOT)
+    import bench
+    off = lambda a: (a.no_kernel_timing, a.no_extra, a.no_cpu_baseline)
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "3"])
+    assert not plain.full and off(plain) == (True, True, True)
+    assert (plain.steps, plain.warmup, plain.blocks, plain.dump_outputs) == (20, 3, 3, None)
+    full = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "3", "--full"])
+    assert full.full and off(full) == (False, False, False)
+    assert off(bench.parse_args(["--full", "--no-extra", "--no-cpu-baseline"])) == (False, True, True)
+    assert off(bench.parse_args(["--full", "--no-kernel-timing"])) == (True, False, False)
+    dp = bench.parse_args(["--force-dp-extras", "--only-dp-breakdown"])
+    assert dp.full and off(dp) == (False, False, False)
+
+
 @pytest.mark.parametrize("rank", [0, 1])
 def test_multi_gpu_extras_deadline_prints_the_headline_and_every_rank_leaves(rank):
     """A collective that never completes inside a multi-GPU `extra` must not take the measured headline down: on expiry

@@ -84,6 +84,28 @@ def test_bench_under_launcher_reports_joined_ranks():
     assert out["value"] > 0 and out["config"]["global_batch"] == 8192 and "roofline" in out
 
 
+@pytest.mark.timeout(900)
+def test_bench_plain_run_is_the_headline_and_full_adds_the_kernel_table():
+    """A plain bench.py run times the steps and prints the line, nothing more: no per-kernel table, no `extra`, no CPU
+    baseline, `roofline` = the whole-step figure.  `--full` runs the HIP-event block and reports the dominant kernel."""
+    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--blocks", "1",
+            "--batch", "8192"]
+    lines = {}
+    for key, more in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-extra"])):
+        r = subprocess.run(args + more, capture_output=True, text=True, timeout=400, env=_env(), cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines[key] = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    plain, full = lines["plain"], lines["full"]
+    for out in (plain, full):
+        assert out["value"] > 0 and out["ms_per_step"] > 0 and out["config"]["global_batch"] == 8192
+        assert out["unit"] == "samples/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    for key in ("extra", "cpu_baseline", "roofline_by_kernel", "ms_per_step_kernel_timing"):
+        assert key not in plain, key
+    assert plain["roofline"] == dict(plain["step_roofline"], traffic=None)
+    assert full["ms_per_step_kernel_timing"] > 0 and full["roofline"]["kernel"] in full["roofline_by_kernel"]
+    assert "extra" not in full and "cpu_baseline" not in full
+
+
 def test_workspace_cache_is_lru_and_never_evicts_a_graph_workspace():
     from dib_amd.engine import HipEngine
     eng = HipEngine([1, 1], [32, 32], [16], 1, feature_embedding_dimension=32)

@@ -8,7 +8,7 @@
 for rep in $(seq 1 ${REPS:-1}); do
 for v in "$@"; do
   o=gpurun_out/exp_${v}${TAG:+_$TAG}
-  DIB_LIB_PATH=exp/lib_$v.so timeout 180 python bench.py --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline --no-extra ${BATCH:+--batch $BATCH} > $o.json 2> $o.err
+  DIB_LIB_PATH=exp/lib_$v.so timeout 180 python bench.py --steps ${STEPS:-20} --warmup 3 --full --no-cpu-baseline --no-extra ${BATCH:+--batch $BATCH} > $o.json 2> $o.err
   python - <<PY
 import json
 d=json.load(open("$o.json"))
