@@ -42,6 +42,7 @@ constexpr int kMaxSplits = 32;   // partial slabs of a split-batch weight gradie
 // Row-tile kernels of dib_small.h: hard limits (they size workspace regions); WHICH batches take them is the "small_wgs" rule
 constexpr int kSmallMaxBatch = 2048;     // rows
 constexpr int kSmallMaxEncWgs = 1024;    // row tiles x features (d(W1|b1) partials: one [16][H1] block per encoder workgroup)
+constexpr size_t kSmallMaxLds = 160 * 1024;   // LDS one workgroup of a row-tile kernel may have (gfx950: the CU's 160 KB)
 constexpr int kSplitRows = 512;  // minimum batch rows per wgrad split: 8 K-tiles of 64 (measured: 2048 left mid-size batches with 16-256 workgroups)
 inline int64_t align_up(int64_t v, int64_t a = kAlign) { return (v + a - 1) / a * a; }
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
@@ -558,6 +559,14 @@ static int fused_encoder_bwd(dib_layout* l, const dib_layout::WsMap& m, float* w
 }
 
 // ---- small-batch row-tile path (dib_small.h) ---------------------------------------------------------------------
+// dynamic LDS bytes of dib_small_encoder_fwd_kernel (bwd = false) / dib_small_encoder_bwd_kernel (bwd = true): their [16][pitch]
+// tiles - input [16][20], h1, h2, d(mu|logvar) (the backward also dh2, dh1) - and the slice primitives' wide exchange buffer.
+// dib_layout_create admits a layout to the row-tile encoders only where both fit kSmallMaxLds.
+static size_t small_encoder_lds(int H1, int H2, int E, bool bwd) {
+  const int k = bwd ? 2 : 1;
+  return (size_t)DIB_SMALL_ROWS * (20 + k * dib_small_pitch(H1) + k * dib_small_pitch(H2) + dib_small_pitch(2 * E)) * sizeof(float) +
+         (size_t)DIB_SMALL_XCH_FLOATS_WIDE * sizeof(float);
+}
 // dynamic LDS above 64 KB needs hipFuncAttributeMaxDynamicSharedMemorySize (per device): raised to what a launch needs
 static int ensure_dynamic_lds(const void* fn, size_t bytes, int (&have)[64]) {
   if (bytes <= 64 * 1024) return DIB_OK;
@@ -604,8 +613,7 @@ static int small_encoder_fwd(dib_layout* l, const dib_layout::WsMap& m, float* w
   a.P = infer ? nullptr : w + m.P; a.h1 = infer ? nullptr : w + m.enc_h[0]; a.h2 = infer ? nullptr : w + m.enc_h[1];
   a.enc_out = w + m.enc_out; a.U = w + m.U; a.kl_partial = w + m.kl_partial;
   a.seed = seed; a.step = step; a.deterministic = flags & DIB_FWD_DETERMINISTIC; a.step_dev = l->step_dev;
-  const size_t lds = (size_t)DIB_SMALL_ROWS * (20 + dib_small_pitch(a.H1) + dib_small_pitch(a.H2) + dib_small_pitch(2 * a.E)) * sizeof(float) +
-                     (size_t)DIB_SMALL_XCH_FLOATS_WIDE * sizeof(float);
+  const size_t lds = small_encoder_lds(a.H1, a.H2, a.E, false);
   static int lds_have[64] = {};
   if (int rc = ensure_dynamic_lds((const void*)dib_small_encoder_fwd_kernel, lds, lds_have)) return rc;
   ProfScope ps(kProfOther, st);
@@ -621,8 +629,7 @@ static int small_encoder_bwd(dib_layout* l, const dib_layout::WsMap& m, float* w
   a.act = l->act; a.F = l->F; a.E = l->E; a.H1 = l->enc_units[0]; a.H2 = l->enc_units[1];
   a.h1 = w + m.enc_h[0]; a.h2 = w + m.enc_h[1]; a.enc_out = w + m.enc_out; a.U = w + m.U; a.GU = w + m.g_u;
   a.dout = w + m.dout; a.dh2 = w + m.g_enc_h[1]; a.dw1_partial = w + m.dw1_partial; a.beta_dev = beta_dev; a.inv_bg = inv_bg;
-  const size_t lds = (size_t)DIB_SMALL_ROWS * (20 + 2 * dib_small_pitch(a.H1) + 2 * dib_small_pitch(a.H2) + dib_small_pitch(2 * a.E)) * sizeof(float) +
-                     (size_t)DIB_SMALL_XCH_FLOATS_WIDE * sizeof(float);
+  const size_t lds = small_encoder_lds(a.H1, a.H2, a.E, true);
   static int lds_have[64] = {};
   if (int rc = ensure_dynamic_lds((const void*)dib_small_encoder_bwd_kernel, lds, lds_have)) return rc;
   ProfScope ps(kProfOther, st);
@@ -691,7 +698,7 @@ static int small_cluster_size(const DibSmallIntArgs& a, size_t lds_bytes, int ot
   // budget - every workgroup must be resident for the networks to run side by side; 2 per tile measured no gain
   // (profiles/r06u_int_cluster_sweep.txt)
   while (cl > 4 && small_tiles(a.batch) * cl + other_wgs > budget) cl >>= 1;
-  if (cl <= 1 || small_tiles(a.batch) * cl + other_wgs > budget || lds_bytes > 160 * 1024) return 1;
+  if (cl <= 1 || small_tiles(a.batch) * cl + other_wgs > budget || lds_bytes > kSmallMaxLds) return 1;
   if (a.mode & (DIB_SMALL_INT_HEAD_REDUCE)) return 1;   // (its last-arriver reduce counts workgroups, not tiles)
   long long weights = 0;
   for (int i = 0, k = a.K0; i < a.n_hidden; k = a.width[i], ++i) weights += (long long)k * a.width[i];
@@ -730,6 +737,9 @@ static int small_integration(dib_layout* l, const dib_layout::WsMap& m, float* w
       ccl = 1;
       cl = small_cluster_size(a, (size_t)l->sb_int_lds + cl_extra, small_tiles(c.batch));
     }
+    // the cluster grid carries BOTH networks' tiles and the wide exchange buffer: each network fitting on its own is not enough
+    // (a companion above 140 KB next to a clustered network) - then both run one workgroup per tile in the plain paired grid
+    if (std::max((size_t)l->sb_int_lds, t_companion.lds) + cl_extra > kSmallMaxLds) cl = ccl = 1;
     if (cl > 1 || ccl > 1) {
       p.s[0].cl = cl; p.s[0].cl_sync = (unsigned*)(w + m.cl_sync);
       p.s[0].cl_agent_scope = c.cl_agent_scope = knobs().int_cluster_short_exchange ? 0 : 1;
@@ -921,15 +931,19 @@ int dib_layout_create(int F, const int* feature_dims, int n_enc, const int* enc_
       for (int f = 0; f < F; ++f) l->fused_offs.push_back(0);
     for (int f = 0; f < F; ++f) l->featmap.push_back(make_int4(l->dims[f], l->in_dim[f], l->x_off[f], l->in_off[f]));
   }
-  // small-batch row-tile kernels (dib_small.h): two-hidden-layer encoders of widths % 16 == 0 with inputs <= 15 wide (the 16th
-  // row of the d(W1|b1) tile carries the bias gradient), linear / relu / leaky_relu; integration networks of 1-3 hidden layers of widths
-  // % 16 == 0 (<= 1024 for the head's lane-strided dot) whose 16-row activation tiles fit the CU's LDS
+  // small-batch row-tile kernels (dib_small.h): two-hidden-layer encoders of widths % 16 == 0 (<= 1024, E <= 512) with inputs
+  // <= 15 wide (the 16th row of the d(W1|b1) tile carries the bias gradient) whose forward AND backward tiles, wide exchange buffer
+  // included (small_encoder_lds), fit one workgroup's 160 KB of LDS - [448, 448] at E = 32 does (162 304 B for the backward),
+  // [512, 512] or [1024, 16] do not; linear / relu / leaky_relu.  Integration networks of 1-3 hidden layers of widths % 16 == 0
+  // (<= 1024 for the head's lane-strided dot) whose 16-row activation tiles fit 150 KB (cluster mode adds 20 KB of exchange buffer)
   {
     bool in_ok = true;
     for (int f = 0; f < F; ++f) in_ok = in_ok && l->in_dim[f] <= 15;
     const bool pl_act = act >= 0 && act <= 2 && out_act >= 0 && out_act <= 2;   // piecewise-linear activations (dib_small.h)
     l->sb_enc = pl_act && n_enc == 2 && in_ok && enc_units[0] % 16 == 0 && enc_units[1] % 16 == 0 && (2 * E) % 16 == 0 &&
-                enc_units[0] <= 1024 && enc_units[1] <= 1024 && E <= 512;
+                enc_units[0] <= 1024 && enc_units[1] <= 1024 && E <= 512 &&
+                small_encoder_lds(enc_units[0], enc_units[1], E, false) <= kSmallMaxLds &&
+                small_encoder_lds(enc_units[0], enc_units[1], E, true) <= kSmallMaxLds;
     bool w_ok = n_int >= 1 && n_int <= 3 && (F * E) % 16 == 0;
     int64_t fl = (int64_t)DIB_SMALL_ROWS * dib_small_pitch(F * E);
     for (int i = 0; i < n_int && w_ok; ++i) {
