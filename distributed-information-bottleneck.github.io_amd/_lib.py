@@ -206,6 +206,12 @@ SIGNATURES_ST = {
     "dib_loss_rows_workspace_bytes": (c_int64, [c_int]),
     "dib_loss_rows": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p,
                               c_void_p]),
+    "dib_mi_probe_map_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "dib_mi_probe_map": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_float, c_uint64,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dib_mi_sandwich_batched_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "dib_mi_sandwich_batched": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_float, c_uint64, c_uint32, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 # include/dib_measure.h: the chaos notebook's measurement-partition model

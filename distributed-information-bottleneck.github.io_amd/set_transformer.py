@@ -71,6 +71,83 @@ def convert_to_per_particle_feature_set(particle_positions, types, number_partic
     return feats
 
 
+def notebook_probe_grid(grid_bound: float = 3.0, grid_side_length: int = 100) -> np.ndarray:
+    """Cell 8's probe positions: a grid_side_length x grid_side_length grid on [-grid_bound, grid_bound]^2, [side^2, 2] float32."""
+    xx, yy = np.meshgrid(np.linspace(-grid_bound, grid_bound, grid_side_length), np.linspace(-grid_bound, grid_bound, grid_side_length))
+    return np.stack([xx, yy], -1).reshape([-1, 2]).astype(np.float32)
+
+
+def _gaussian_filter1d(x, sigma: float, truncate: float = 4.0) -> np.ndarray:
+    """scipy.ndimage.gaussian_filter1d(x, sigma) (mode "reflect", truncate 4) for 1-D x; the result keeps x's dtype."""
+    x = np.asarray(x)
+    if x.size == 0 or sigma <= 0:
+        return x.copy()
+    r = int(truncate * float(sigma) + 0.5)
+    k = np.exp(-0.5 * (np.arange(-r, r + 1) / float(sigma)) ** 2)
+    k /= k.sum()
+    xp = np.pad(x.astype(np.float64), r, mode="symmetric")   # scipy's "reflect" = numpy's "symmetric"
+    return np.convolve(xp, k, mode="valid").astype(x.dtype)
+
+
+def information_plane(hist, entropy_y: float = 1.0, smoothing_sigma: float = 1) -> Dict[str, np.ndarray]:
+    """The tail of notebook cell 8 on a fit(track_information=True) history: BCE and bounds to bits, BCE and accuracy
+    smoothed with gaussian_filter1d(sigma), info_in = mean of the two bounds (already x particles), info_out = entropy_y - BCE
+    over the evaluations that have bounds.  Returns the arrays the notebook plots and saves."""
+    bce_series_val = np.float32(hist["bce_series_val"]) / np.log(2)
+    acc_series_val = np.float32(hist["acc_series_val"])
+    info_bounds = np.float32(hist["info_bounds"]).reshape(-1, 2) / np.log(2)
+    info_in = np.mean(info_bounds, axis=-1)
+    bce_smoothed = _gaussian_filter1d(bce_series_val, smoothing_sigma)
+    acc_smoothed = _gaussian_filter1d(acc_series_val, smoothing_sigma)
+    start = -len(info_in)
+    return dict(info_in=info_in, info_out=entropy_y - bce_smoothed[start:], acc=acc_smoothed[start:],
+                validation_bce=bce_series_val, acc_validation=acc_series_val, info_bounds=info_bounds)
+
+
+def save_information_plane(hist, path: str, entropy_y: float = 1.0, smoothing_sigma: float = 1, info_in_plot_lims=(0, 40),
+                           title: Optional[str] = None) -> None:
+    """The notebook's information-plane figure (info out and validation accuracy against total information in, bits)."""
+    import matplotlib
+    matplotlib.use("Agg")
+    import matplotlib.pyplot as plt
+    ip = information_plane(hist, entropy_y, smoothing_sigma)
+    fig = plt.figure(figsize=(10, 6))
+    ax = plt.gca()
+    ax.plot(ip["info_in"], ip["info_out"], lw=4, color="k")
+    ax.set_ylim(0, None)
+    ax.set_xlim(list(info_in_plot_lims))
+    ax.set_xlabel("Total information into model (bits)", fontsize=15)
+    ax.set_ylabel("Info out (bits)", fontsize=15)
+    ax2 = ax.twinx()
+    ax2.plot(ip["info_in"], ip["acc"], lw=2, color="b")
+    ax2.set_ylabel("ACC (validation)", color="b", fontsize=15)
+    if title:
+        plt.title(title, fontsize=15)
+    fig.savefig(path)
+    plt.close(fig)
+
+
+def save_information_map(grids, path: str, masks=None, info_cmap: str = "gist_heat_r") -> None:
+    """The notebook's per-type information maps (mean of the two bounds, bits) side by side; grids [types, side^2 or side x
+    side, 2] nats; masks (optional) [types][side, side] of 1 / NaN (the notebook blanks the centre from the g(r) files)."""
+    import matplotlib
+    matplotlib.use("Agg")
+    import matplotlib.pyplot as plt
+    grids = np.asarray(grids, dtype=np.float64)
+    side = int(round(math.sqrt(grids.shape[1] if grids.ndim == 3 else grids.shape[1] * grids.shape[2])))
+    fig = plt.figure(figsize=(9 * len(grids), 8))
+    for t, g in enumerate(grids):
+        img = np.mean(g.reshape(side, side, 2), axis=-1) / np.log(2)
+        if masks is not None:
+            img = masks[t] * img
+        plt.subplot(1, len(grids), t + 1)
+        plt.imshow(img, info_cmap)
+        plt.axis("off")
+        plt.colorbar()
+    fig.savefig(path)
+    plt.close(fig)
+
+
 class _SplitKGemm:
     """A skinny product C[M, N] = A[M, K] @ W (N = the model width, 32; K = heads * key_dim = 1536) with FEW row tiles: the
     output has ceil(M / 64) workgroups' worth of tiles and each would walk all of K with one tile of prefetch - at the
@@ -1148,6 +1225,111 @@ class SetTransformerDIB:
                 up_acc[sl] += up
         return torch.stack([lo_acc, up_acc], -1).cpu().numpy() / num_eval_batches
 
+    # ---- information tracking: one launch per estimate over the encoded validation set (include/dib_st.h dib_mi_probe_map /
+    # dib_mi_sandwich_batched, csrc/dib_st_info.h) --------------------------------------------------------------------------------
+    def _val_table(self, particle_features_val):
+        """(particle_encoder outputs of every validation particle [N_val * P, 2E] on the device, N_val, P)."""
+        xv = particle_features_val
+        if not isinstance(xv, torch.Tensor):
+            xv = torch.from_numpy(np.ascontiguousarray(xv, dtype=np.float32))
+        if xv.dim() != 3 or xv.shape[-1] != self.particle_feature_dimensions:
+            raise ValueError(f"particle_features_val must be [neighbourhoods, particles, {self.particle_feature_dimensions}], got "
+                             f"{tuple(xv.shape)}")
+        n_val, P = int(xv.shape[0]), int(xv.shape[1])
+        enc = self.particle_encoder(xv.reshape(n_val * P, self.particle_feature_dimensions)).contiguous()
+        return enc, n_val, P
+
+    def _f64_workspace(self, nbytes: int) -> torch.Tensor:
+        ws = getattr(self, "_info_ws", None)
+        if ws is None or ws.numel() * 8 < nbytes:
+            ws = self._info_ws = torch.empty(max(int(nbytes) // 8 + 2, 2), dtype=torch.float64, device=self.device)
+        return ws
+
+    def sandwich_bounds_batched(self, table, nbhd_idx, seed: int = 0, step: int = 0, logvar_offset: Optional[float] = None,
+                                return_rows: bool = False, return_samples: bool = False):
+        """dib_mi_sandwich_batched on an encoded table (enc, N_val, P) and neighbourhood indices [nb, n_nbhd]: per-batch
+        (lower, upper) means [nb] (nats, float64 device tensors), optionally per-row bounds [nb, n] and the samples [nb, n, E]."""
+        enc, n_val, P = table
+        idx = np.ascontiguousarray(nbhd_idx, dtype=np.int64)
+        if idx.ndim != 2 or idx.size == 0 or idx.min() < 0 or idx.max() >= n_val:
+            raise ValueError("nbhd_idx must be a non-empty [batches, neighbourhoods] array of indices into the table")
+        nb, nn = idx.shape
+        E = self.bottleneck_dimension
+        lv = self.logvar_initialization if logvar_offset is None else float(logvar_offset)
+        need = int(self.lib.dib_mi_sandwich_batched_workspace_bytes(n_val, P, E, nb, nn))
+        if need < 0:
+            raise ValueError(f"dib_mi_sandwich_batched: unsupported shape (batches {nb}, neighbourhoods {nn}, particles {P}, E {E})")
+        ws = self._f64_workspace(need)
+        idx_d = torch.from_numpy(idx.astype(np.int32)).to(self.device)
+        out = torch.empty((2, nb), dtype=torch.float64, device=self.device)
+        rows = torch.empty((2, nb, nn * P), dtype=torch.float64, device=self.device) if return_rows else None
+        u = torch.empty((nb, nn * P, E), dtype=torch.float64, device=self.device) if return_samples else None
+        check(self.lib.dib_mi_sandwich_batched(_ptr8(enc), n_val, P, E, _ptr8(idx_d), nb, nn, lv, int(seed) & (2 ** 64 - 1),
+                                               int(step) & 0xFFFFFFFF, _ptr8(out[0]), _ptr8(out[1]),
+                                               _ptr8(rows[0]) if rows is not None else c_void_p(0),
+                                               _ptr8(rows[1]) if rows is not None else c_void_p(0), _ptr8(u), _ptr8(ws),
+                                               self._stream()), "dib_mi_sandwich_batched")
+        res = (out[0], out[1])
+        if return_rows:
+            res += (rows[0], rows[1])
+        if return_samples:
+            res += (u,)
+        return res
+
+    def information_bounds(self, particle_features_val, eval_batch_size: int = 32, num_eval_batches: int = 16, seed: int = 0,
+                           step: int = 0, _table=None) -> Tuple[float, float]:
+        """Cell 8's "Evaluate I(U;X)": num_eval_batches batches of eval_batch_size validation neighbourhoods (drawn with
+        replacement by default_rng(seed).choice), all their particles encoded (logvar - 3), cell 5's compute_infos_mus_logvars
+        per batch (InfoNCE lower / leave-one-out upper over the batch's conditionals, float64, log-sum-exp; noise keyed
+        (seed, step + batch, row, 0)).  Returns (mean(lower), mean(upper)) per particle in nats - the notebook stores them
+        x number_particles_to_use.  The validation set is encoded once and all batches run in one launch."""
+        table = _table if _table is not None else self._val_table(particle_features_val)
+        rng = np.random.default_rng(seed)
+        idx = np.stack([rng.choice(table[1], size=int(eval_batch_size)) for _ in range(int(num_eval_batches))])
+        lo, up = self.sandwich_bounds_batched(table, idx, seed=seed, step=step)
+        return float(np.mean(lo.cpu().numpy())), float(np.mean(up.cpu().numpy()))
+
+    def information_maps(self, particle_positions_probe, particle_features_val, type_ids: Sequence[int] = (0, 1),
+                         num_eval_batches: int = 16, eval_batch_size_probe_grid: int = 512,
+                         number_probes_to_eval_at_a_time: int = 100, seed: int = 0, _table=None, _return_samples: bool = False):
+        """information_map for several particle types at once: returns [len(type_ids), n_probes, 2] (nats); for each type the
+        same index draws (default_rng(seed), chunk by chunk, batch by batch), the same noise keys and the same formulas as
+        information_map(positions, type_id, particle_features_val, ..., seed=seed), with the validation set encoded once and
+        every (chunk, batch) of a type in ONE launch of dib_mi_probe_map."""
+        pos = np.asarray(particle_positions_probe, dtype=np.float32).reshape(-1, 2)
+        table = _table if _table is not None else self._val_table(particle_features_val)
+        enc, n_val, P = table
+        M, C, nb, nbs = pos.shape[0], int(number_probes_to_eval_at_a_time), int(num_eval_batches), int(eval_batch_size_probe_grid)
+        E = self.bottleneck_dimension
+        if M <= 0 or C <= 0 or nb <= 0 or nbs <= 0:
+            raise ValueError("information_maps needs probes, a chunk size, batches and a batch size > 0")
+        n_chunks = (M + C - 1) // C
+        steps = np.array([[(c * C * 131 + b) & 0xFFFFFFFF for b in range(nb)] for c in range(n_chunks)], dtype=np.uint32)
+        steps_d = torch.from_numpy(steps.view(np.int32)).to(self.device)
+        need = int(self.lib.dib_mi_probe_map_workspace_bytes(M, C, n_val, P, E, nb, nbs))
+        if need < 0:
+            raise ValueError(f"dib_mi_probe_map: unsupported shape (probes {M}, chunk {C}, batches {nb}, neighbourhoods {nbs}, E {E})")
+        ws = self._f64_workspace(need)
+        out = torch.empty((len(type_ids), 2, M), dtype=torch.float64, device=self.device)
+        # information_map restarts default_rng(seed) for every type: every type sees the same draws
+        rng = np.random.default_rng(seed)
+        idx = np.empty((n_chunks, nb, nbs), dtype=np.int32)
+        for c in range(n_chunks):
+            for b in range(nb):
+                idx[c, b] = rng.choice(n_val, size=nbs, replace=True)
+        idx_d = torch.from_numpy(idx).to(self.device)
+        samples = []
+        for ti, type_id in enumerate(type_ids):
+            features = convert_to_per_particle_feature_set(pos, (int(type_id) + 1) * np.ones(M, dtype=np.float32), number_particles_to_use=-1)
+            ep = self.particle_encoder(features).contiguous()
+            u = torch.empty((n_chunks, nb, C, E), dtype=torch.float64, device=self.device) if _return_samples else None
+            check(self.lib.dib_mi_probe_map(_ptr8(ep), M, C, _ptr8(enc), n_val, P, E, _ptr8(idx_d), nb, nbs, self.logvar_initialization,
+                                            int(seed) & (2 ** 64 - 1), _ptr8(steps_d), _ptr8(out[ti, 0]), _ptr8(out[ti, 1]), _ptr8(u),
+                                            _ptr8(ws), self._stream()), "dib_mi_probe_map")
+            samples.append((ep, u))
+        grids = out.transpose(1, 2).cpu().numpy()
+        return (grids, samples) if _return_samples else grids
+
     # ---- the notebook's training loop ------------------------------------------------------------------------------------
     @staticmethod
     def learning_rate_schedule(step: int, learning_rate: float, number_training_steps: int) -> float:
@@ -1161,15 +1343,33 @@ class SetTransformerDIB:
 
     def fit(self, particle_features_train, loci_train, number_training_steps=25_000, learning_rate=1e-4, beta_start=2e-6,
             beta_end=2e-1, batch_size=32, particle_features_val=None, loci_val=None, eval_every=None, batch_seed=0,
-            verbose=False):
+            verbose=False, track_information=False, eval_start=None, num_eval_batches=16, eval_batch_size=32,
+            particle_positions_probe=None, eval_grid_mi_every=1000, eval_batch_size_probe_grid=512, info_seed=0, outdir=None):
         """The notebook's loop: per step ramp the learning rate, anneal beta, draw `batch_size` neighbourhoods with
         replacement, train_step; every `eval_every` steps evaluate BCE and accuracy (sign of the logit) on the validation
-        neighbourhoods.  Returns dict(bce_series_val, acc_series_val, bce_series_train)."""
+        neighbourhoods.  Returns dict(bce_series_val, acc_series_val, bce_series_train).
+        track_information=True adds cell 8's information tracking (needs the validation set): at every evaluation from
+        eval_start (default number_training_steps // 4) on, information_bounds over num_eval_batches x eval_batch_size
+        neighbourhoods -> info_bounds [[P lower, P upper]] (nats, as the notebook stores them) and info_eval_steps; at those of
+        them that are multiples of eval_grid_mi_every, information_maps of both particle types on particle_positions_probe
+        (default: the notebook's 100 x 100 grid on [-3, 3]^2) -> information_maps {step: [2, probes, 2]}.  The evaluation draws
+        from its own generators (seeded from info_seed and the step) and noise keys: the training batches, noise and optimizer
+        state are those of the untracked run.  outdir: also write the notebook's history.npz (bits) and
+        info_bounds_grid_{step}_type{t}.npy ([side, side, 2], nats)."""
         xtr = torch.from_numpy(np.ascontiguousarray(particle_features_train, dtype=np.float32)).to(self.device)
         ytr = torch.from_numpy(np.ascontiguousarray(loci_train, dtype=np.float32).reshape(-1, 1)).to(self.device)
         rng = np.random.default_rng(batch_seed)
         eval_every = eval_every or max(number_training_steps // 200, 1)
         hist = dict(bce_series_val=[], acc_series_val=[], bce_series_train=[], eval_steps=[])
+        if track_information:
+            if particle_features_val is None:
+                raise ValueError("track_information needs particle_features_val")
+            eval_start = number_training_steps // 4 if eval_start is None else int(eval_start)
+            probes = notebook_probe_grid() if particle_positions_probe is None else np.asarray(particle_positions_probe, np.float32)
+            xv_dev = torch.from_numpy(np.ascontiguousarray(particle_features_val, dtype=np.float32)).to(self.device)
+            hist.update(info_bounds=[], info_eval_steps=[], information_maps={})
+            if outdir:
+                os.makedirs(outdir, exist_ok=True)
         for step in range(number_training_steps):
             self.lr_dev.fill_(self.learning_rate_schedule(step, learning_rate, number_training_steps))
             self.beta_dev.fill_(self.beta_schedule(step, beta_start, beta_end, number_training_steps))
@@ -1192,4 +1392,31 @@ class SetTransformerDIB:
                     hist["eval_steps"].append(step)
                     if verbose:
                         print(f"Step: {step}, acc : {right / n:.4f}")
+                    if track_information and step >= eval_start:
+                        self._track_information(hist, step, xv_dev, probes, num_eval_batches, eval_batch_size, eval_grid_mi_every,
+                                                eval_batch_size_probe_grid, info_seed, outdir)
+        if track_information and outdir:
+            np.savez(os.path.join(outdir, "history.npz"), validation_bce=np.float32(hist["bce_series_val"]) / np.log(2),
+                     acc_validation=np.float32(hist["acc_series_val"]),
+                     info_bounds=np.float32(hist["info_bounds"]).reshape(-1, 2) / np.log(2))
         return hist
+
+    def _track_information(self, hist, step, xv_dev, probes, num_eval_batches, eval_batch_size, eval_grid_mi_every,
+                           eval_batch_size_probe_grid, info_seed, outdir):
+        """One evaluation of fit(track_information=True): I(U;X) bounds, and on map steps both particle types' maps, from one
+        encoding of the validation set at the current parameters."""
+        table = self._val_table(xv_dev)
+        P = table[2]
+        base = (int(info_seed) << 32) + 2 * int(step)   # generator / noise seeds of this evaluation: bounds base, maps base + 1
+        lo, up = self.information_bounds(None, eval_batch_size, num_eval_batches, seed=base, step=0, _table=table)
+        hist["info_bounds"].append([P * lo, P * up])
+        hist["info_eval_steps"].append(step)
+        if step % eval_grid_mi_every == 0:
+            grids = self.information_maps(probes, None, (0, 1), num_eval_batches, eval_batch_size_probe_grid, 100, seed=base + 1,
+                                          _table=table)
+            hist["information_maps"][step] = grids
+            if outdir:
+                side = int(round(math.sqrt(grids.shape[1])))
+                for t in range(grids.shape[0]):
+                    g = grids[t].reshape(side, side, 2) if side * side == grids.shape[1] else grids[t]
+                    np.save(os.path.join(outdir, f"info_bounds_grid_{step}_type{t}.npy"), g)

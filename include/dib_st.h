@@ -170,6 +170,33 @@ int dib_mi_probe_bounds(const float* enc_probe, int n_probes, const float* enc_d
                         uint64_t seed, uint32_t step, uint32_t feature, double* lower_rows, double* upper_rows,
                         double* u_probe_out, void* ws, dib_stream_t stream);
 
+/* The same estimators over an ENCODED TABLE of validation particles in one tiled launch each (csrc/dib_st_info.h; notebook
+ * cell 8's I(U;X) evaluation and its probe-grid map).  enc_table [n_table_nbhd * P, 2E] = particle_encoder outputs (mu | raw
+ * logvar) of every validation particle; a batch names neighbourhoods, neighbourhood k contributes rows k P .. k P + P - 1 (device
+ * int32 indices; an index outside [0, n_table_nbhd) makes the affected results NaN).  logvar_offset is added in double.
+ * float64, log-sum-exp, deterministic (no atomics: per-workgroup partials merged in a fixed order).  E % 4 == 0, E <= 256.
+ *
+ * dib_mi_probe_map: probes enc_probe [n_probes, 2E] in chunks of `chunk`; nbhd_idx [n_chunks][nb][n_nbhd], steps [n_chunks][nb]
+ * (device).  For probe i of chunk c and batch b one sample u = mu_i + sigma_i eps, eps keyed (seed, steps[c][b], row i - c chunk,
+ * feature 0) - the keys of dib_mi_probe_bounds - and with N = n_nbhd P data rows
+ *   lower_b = l_ii - (LSE(l_ii, l_i1 .. l_iN) - log(N + 1)),  upper_b = l_ii - (LSE(l_i1 .. l_iN) - log N);
+ * lower[i] / upper[i] = their means over the nb batches (summed in batch order).  u_out (optional) [n_chunks][nb][chunk][E].
+ *
+ * dib_mi_sandwich_batched: nbhd_idx [nb][n_nbhd]; batch b = its n = n_nbhd P rows, row i sampled with the keys of
+ * dib_mi_sandwich_rows (seed, step + b, row i, feature 0);
+ *   lower_i = l_ii - (LSE_j l_ij - log n),  upper_i = l_ii - (LSE_{j != i} l_ij - log n)   (j != i by position: repeated rows count)
+ * lower_batches / upper_batches [nb] = the per-batch means; lower_rows / upper_rows (optional, both or neither) [nb][n];
+ * u_out (optional) [nb][n][E].  n >= 2.
+ * ws: the matching *_workspace_bytes (16-byte aligned).  DIB_E_ARG outside the envelope. */
+int64_t dib_mi_probe_map_workspace_bytes(int n_probes, int chunk, int n_table_nbhd, int P, int E, int nb, int n_nbhd);
+int dib_mi_probe_map(const float* enc_probe, int n_probes, int chunk, const float* enc_table, int n_table_nbhd, int P, int E,
+                     const int32_t* nbhd_idx, int nb, int n_nbhd, float logvar_offset, uint64_t seed, const uint32_t* steps,
+                     double* lower, double* upper, double* u_out, void* ws, dib_stream_t stream);
+int64_t dib_mi_sandwich_batched_workspace_bytes(int n_table_nbhd, int P, int E, int nb, int n_nbhd);
+int dib_mi_sandwich_batched(const float* enc_table, int n_table_nbhd, int P, int E, const int32_t* nbhd_idx, int nb, int n_nbhd,
+                            float logvar_offset, uint64_t seed, uint32_t step, double* lower_batches, double* upper_batches,
+                            double* lower_rows, double* upper_rows, double* u_out, void* ws, dib_stream_t stream);
+
 /* Keras loss on plain buffers (DIB_LOSS_* of dib_hip.h): out3 = {sum of per-row losses, #correct, rows};
  * g_pred = d(mean loss)/d(pred) * (inv_global_batch * batch). */
 int64_t dib_loss_rows_workspace_bytes(int batch);

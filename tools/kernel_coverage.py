@@ -61,6 +61,9 @@ ORACLE_TESTS = {
         "test_softmax_rows_forward_backward_vs_float64", "test_add_layernorm_forward_backward_vs_float64", "test_act_grad_mul_vs_numpy",
         "test_sgd_step_vs_numpy", "test_gemm_tile_shapes_the_default_rules_rarely_pick", "test_weight_gradient_flat_tile_vs_numpy", "test_attention_forward_with_projections_vs_float64", "test_attention_backward_with_projection_gradient_vs_float64"},
     "test_gpu_small_envelope.py": {"test_row_tile_envelope_step_matches_oracle", "test_paired_grid_matches_oracle"},
+    "test_gpu_st_information.py": {
+        "test_batched_sandwich_bounds_match_oracle", "test_probe_map_matches_oracle", "test_far_apart_gaussians_stay_finite",
+        "test_notebook_batch_size_on_a_subset_of_probes", "test_information_bounds_match_the_oracle_on_the_model_encodings"},
 }
 # tests that demand the bits (or fp32 summation-order tolerance) of a path the tests above check against an oracle
 EQUIVALENCE_TESTS = {
@@ -78,6 +81,10 @@ EQUIVALENCE_TESTS = {
         "test_fit_under_rccl_one_rank_equals_single_process", "test_three_bucket_backward_hooks_equal_the_plain_backward",
         "test_set_transformer_train_step_under_rccl_one_rank_equals_single_process"},
     "test_gpu_concurrency.py": {"test_two_threads_two_streams_equal_the_serial_run"},
+    "test_gpu_st_information.py": {
+        "test_batched_sandwich_equals_the_per_batch_rows_loop", "test_probe_map_equals_the_probe_bounds_loop",
+        "test_information_maps_equal_information_map", "test_replay_is_bit_identical_and_bad_arguments_are_refused",
+        "test_tracked_fit_trains_exactly_like_the_untracked_fit"},
 }
 
 
