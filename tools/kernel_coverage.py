@@ -61,6 +61,8 @@ ORACLE_TESTS = {
         "test_softmax_rows_forward_backward_vs_float64", "test_add_layernorm_forward_backward_vs_float64", "test_act_grad_mul_vs_numpy",
         "test_sgd_step_vs_numpy", "test_gemm_tile_shapes_the_default_rules_rarely_pick", "test_weight_gradient_flat_tile_vs_numpy", "test_attention_forward_with_projections_vs_float64", "test_attention_backward_with_projection_gradient_vs_float64"},
     "test_gpu_small_envelope.py": {"test_row_tile_envelope_step_matches_oracle", "test_paired_grid_matches_oracle"},
+    "test_gpu_st_envelope.py": {"test_attention_envelope_matches_float64", "test_attention_with_projections_matches_float64",
+                                "test_token_chain_envelope_matches_float64", "test_model_plan_branches_match_oracle"},
     "test_gpu_st_information.py": {
         "test_batched_sandwich_bounds_match_oracle", "test_probe_map_matches_oracle", "test_far_apart_gaussians_stay_finite",
         "test_notebook_batch_size_on_a_subset_of_probes", "test_information_bounds_match_the_oracle_on_the_model_encodings"},
