@@ -1,5 +1,5 @@
 """Grouped-GEMM launch records shared by the host classes that drive `dib_gemm_grouped` (include/dib_st.h) directly:
-SetTransformerDIB (set_transformer.py) and DenseStack (dense.py).  A `_Gemm` is one launch: a device-resident descriptor
+SetTransformerDIB (its plans: _st_plan.py) and DenseStack (dense.py).  A `_Gemm` is one launch: a device-resident descriptor
 table (one `dib_gemm_desc` per group: element offsets into the base tensors, leading dimensions, M/N/K) plus the base
 tensors; the tables are built and uploaded once per batch shape, so a step is a sequence of C-ABI calls with no per-call
 descriptor traffic."""
@@ -28,9 +28,14 @@ def _ptr8(t: Optional[torch.Tensor]):
     return c_void_p(t.data_ptr()) if t is not None else c_void_p(0)
 
 
+def _ptr_array3(t: torch.Tensor, offs):
+    """void*[3] of up to three regions of `t` (element offsets), NULL beyond: the per-layer row buffers of dib_mlp_small_*"""
+    return (c_void_p * 3)(*([_ptr(t, o).value for o in offs] + [None] * (3 - len(offs))))
+
 
 class _Gemm:
-    """One grouped-GEMM launch: a device descriptor table + base tensors."""
+    """One grouped-GEMM launch: a device descriptor table + base tensors.  A base tensor may be given by NAME when the table
+    is built before its memory exists; `bind` resolves the names."""
 
     def __init__(self, mode, descs, A, B, C, bias=None, aux=None, bias_out=None, act=0, nsplit=1, rows_per_split=0,
                  split_stride=0):
@@ -38,13 +43,17 @@ class _Gemm:
         self.max_m = int(max(d["M"] for d in descs))
         self.max_n = int(max(d["N"] for d in descs))
         arr = np.zeros(len(descs), dtype=DESC)
-        for i, d in enumerate(descs):
-            for k, v in d.items():
-                arr[i][k] = v
+        for k in descs[0]:   # (all descriptors of a table come from the same constructor: same fields)
+            arr[k] = [d[k] for d in descs]
         self.host = arr
         self.dev = None
         self.A, self.B, self.C, self.bias, self.aux, self.bias_out = A, B, C, bias, aux, bias_out
         self.act, self.nsplit, self.rps, self.stride = act, nsplit, rows_per_split, split_stride
+
+    def bind(self, bases):
+        for k in ("A", "B", "C", "bias", "aux", "bias_out"):
+            if isinstance(getattr(self, k), str):
+                setattr(self, k, bases[getattr(self, k)])
 
     def upload(self, device):
         self.dev = torch.from_numpy(self.host.view(np.uint8).copy()).to(device)
@@ -53,7 +62,6 @@ class _Gemm:
         check(lib.dib_gemm_grouped(self.mode, self.n, _ptr(self.dev), self.max_m, self.max_n, _ptr(self.A), _ptr(self.B),
                                    _ptr(self.C), _ptr(self.bias), _ptr(self.aux), _ptr(self.bias_out), self.act, self.nsplit,
                                    self.rps, self.stride, stream), "dib_gemm_grouped")
-
 
 
 class _SkinnyKGemm(_Gemm):
@@ -77,3 +85,31 @@ def _d(a_off, lda, b_off, ldb, c_off, ldc, M, N, K, bias_off=-1, aux_off=0, ldau
                 ldc=ldc, ldaux=ldaux)
 
 
+class _SplitKGemm:
+    """A skinny product C[M, N] = A[M, K] @ W (N = the model width, 32; K = heads * key_dim = 1536) with FEW row tiles: the
+    output has ceil(M / 64) workgroups' worth of tiles and each would walk all of K with one tile of prefetch - at the
+    notebook's size (1600 tokens) 25 workgroups x 48 dependent k-tiles = 84 us for 0.16 GFLOP, the two slowest launches of
+    the whole step.  Here the contraction is cut into `ksplit` chunks that run as extra GROUPS of the same grouped launch
+    (one partial slab each), summed in a fixed order by dib_reduce_splits: deterministic, no new kernel."""
+
+    def __init__(self, gemm: _Gemm, partial, partial_off, n, nslabs, out, out_off, mode: str = "store"):
+        """mode: "store" out = sum of the slabs; "add" out += sum (a residual branch's gradient joins the one already there:
+        one launch instead of reduce + add); "defer" no reduce here - the consumer sums the slabs itself
+        (dib_add_layernorm_fwd's b_slabs)."""
+        self.gemm, self.partial, self.partial_off, self.n, self.nslabs, self.out, self.out_off, self.mode = \
+            gemm, partial, partial_off, n, nslabs, out, out_off, mode
+
+    def bind(self, bases):
+        self.gemm.bind(bases)
+        self.partial, self.out = bases[self.partial], bases[self.out]
+
+    def upload(self, device):
+        self.gemm.upload(device)
+
+    def run(self, lib, stream):
+        self.gemm.run(lib, stream)
+        if self.mode == "defer":
+            return
+        fn = lib.dib_reduce_splits_add if self.mode == "add" else lib.dib_reduce_splits
+        check(fn(_ptr(self.partial, self.partial_off), self.n, self.nslabs, self.n, _ptr(self.out, self.out_off), stream),
+              "dib_reduce_splits")

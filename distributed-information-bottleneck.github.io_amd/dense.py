@@ -16,7 +16,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
-from ._gemm_plan import _Gemm, _d, _ptr
+from ._gemm_plan import _Gemm, _d, _ptr, _ptr_array3
 from ._lib import ACTIVATIONS, SYNC_WORDS as _SYNC_WORDS, check
 
 
@@ -27,6 +27,15 @@ class _MlpDesc(ctypes.Structure):
 
 
 assert ctypes.sizeof(_MlpDesc) == 96
+
+
+def _mlp_desc(w_off: Sequence[int], b_off: Sequence[int], widths: Sequence[int], in_dim: int, n_freq: int, act: int) -> _MlpDesc:
+    """dib_mlp_desc of [PositionalEncoding(n_freq)] -> Dense(widths[0], act) ... -> Dense(widths[-1]) (at most 4 layers)"""
+    d = _MlpDesc()
+    for l, u in enumerate(widths):
+        d.w_off[l], d.b_off[l], d.width[l] = w_off[l], b_off[l], u
+    d.n_hidden, d.in_dim, d.n_freq, d.act = len(widths) - 1, in_dim, n_freq, act
+    return d
 
 
 class DenseStack:
@@ -58,11 +67,9 @@ class DenseStack:
         # batches <= 2048 rows: the whole layer chain of 16 rows in one workgroup (dib_mlp_small_fwd / _bwd, csrc/dib_small.h)
         self._desc = None
         if 2 <= len(self.dims) <= 4:
-            d = _MlpDesc()
-            for l in range(len(self.dims)):
-                d.w_off[l], d.b_off[l], d.width[l] = self.w_off[l], self.b_off[l], self.dims[l][1]
-            d.n_hidden, d.in_dim, d.n_freq, d.act = len(self.dims) - 1, self.input_dim, max(self.n_freq, 1), self.act
-            self._desc = d
+            self._desc = _mlp_desc(self.w_off, self.b_off, [o for _, o in self.dims], self.input_dim, max(self.n_freq, 1), self.act)
+        self._unreduced: Optional[dict] = None   # the plan whose slabs a backward(reduce=False) left for the optimizer's launch
+        self._sync: Optional[torch.Tensor] = None   # dib_reduce_adam_step's grid-sync words, allocated by its first call
 
     # views
     def kernel(self, l):
@@ -114,8 +121,7 @@ class DenseStack:
             self._plans.pop(next(iter(self._plans)))
         pl = self._plans[n] = dict(n=n, ws=ws, off=off, g=g, nsplit=nsplit, slabs=slabs, small=False)
         if self._desc is not None:
-            nh = L - 1
-            ptrs = lambda pre: (ctypes.c_void_p * 3)(*[_ptr(ws, off[f"{pre}{l + 1}"]).value if l < nh else None for l in range(3)])
+            ptrs = lambda pre: _ptr_array3(ws, [off[f"{pre}{l + 1}"] for l in range(L - 1)])
             pl.update(h_ptrs=ptrs("a"), g_ptrs=ptrs("g"))
         return pl
 
@@ -240,8 +246,8 @@ class DenseStack:
         if lr is not None:
             self.lr_dev.fill_(float(lr))
         if fused_reduce:
-            pl = getattr(self, "_unreduced", None)
-            if getattr(self, "_sync", None) is None:
+            pl = self._unreduced
+            if self._sync is None:
                 self._sync = torch.zeros(_SYNC_WORDS, dtype=torch.int32, device=self.device)
             check(self.lib.dib_reduce_adam_step(_ptr(pl["slabs"]) if pl is not None else None, pl["nsplit"] if pl is not None else 0,
                                                 self.n_params, _ptr(self.params), _ptr(self.grads), _ptr(self.adam_m),
@@ -249,7 +255,7 @@ class DenseStack:
                                                 beta2, eps, 1.0, _ptr(self._sync), self.eng._stream()), "dib_reduce_adam_step")
             self._unreduced = None
             return
-        assert getattr(self, "_unreduced", None) is None, "backward(reduce=False) must be followed by adam_step(fused_reduce=True)"
+        assert self._unreduced is None, "backward(reduce=False) must be followed by adam_step(fused_reduce=True)"
         check(self.lib.dib_adam_step(_ptr(self.params), _ptr(self.grads), _ptr(self.adam_m), _ptr(self.adam_v),
                                      self.n_params, _ptr(self.lr_dev), _ptr(self.t_dev), beta1, beta2, eps, 1.0,
                                      self.eng._stream()), "dib_adam_step")

@@ -9,11 +9,17 @@ Dense(32, relu) -> Add -> LayerNormalization], tf.reduce_mean over the particle 
 BCE-from-logits + beta * KL, Keras Adam, the linear learning-rate warm-up and the per-STEP log ramp of beta of the
 notebook's training loop.  Same names and argument meaning as the notebook's variables.
 
-Every FLOP runs in libdib_hip.so through the C ABI of include/dib_st.h: all matrix products (encoder, q/k/v/output
-projections, the per-(neighbourhood, head) Q K^T, P V and their four backward products, feed-forward, head, every weight
-gradient) on the grouped fp32-MFMA GEMM (`dib_gemm_grouped`, 12 x batch groups per launch for the attention products),
-softmax / Add+LayerNorm / mean-pool / reparameterisation+KL / loss / Adam as HBM-bound row kernels.  PyTorch only owns the
-device memory.  There is no CPU fallback.
+Every FLOP runs in libdib_hip.so through the C ABI of include/dib_st.h; PyTorch only owns the device memory and there is no
+CPU fallback.  What a (batch, particles) shape runs on is decided once per shape, in one place (_st_plan.decide).  At the
+notebook's size (32 x 50) a training step is 38 launches: encoder and head on the row-tile MLP kernels (`dib_mlp_small_fwd` /
+`_bwd`, `dib_mlp_small_head_step`), per block and direction one flash-attention launch with the q / k / v projections inside
+(`dib_attention_fwd_proj` / `_bwd_proj`, up to 64 particles; beyond, `dib_attention_fwd` / `_bwd` next to projection GEMMs)
+and one launch for the token-wise half (`dib_st_chain_fwd` / `_bwd`: output projection, Add + LayerNorm, feed-forward,
+Add + LayerNorm; up to 4096 tokens), all blocks' weight gradients as one grouped fp32-MFMA GEMM per shape class
+(`dib_gemm_grouped`), slab reduce + Keras Adam in one launch (`dib_reduce_adam_step`).  Outside a kernel's envelope a stage
+takes its general path: grouped GEMMs for every product (attention="gemm" or key_dim != 128: the per-(neighbourhood, head)
+Q K^T, P V and their four backward products as groups, probabilities in HBM), softmax / Add+LayerNorm / mean-pool /
+reparameterisation+KL / loss as row kernels.
 
 Parameters live in one flat fp32 buffer in Keras variable-creation order (`param_shapes`, the order of
 `particle_encoder.trainable_variables + set_transformer.trainable_variables`), every block 16-byte aligned.
@@ -30,29 +36,15 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._gemm_plan import DESC, _Gemm, _SkinnyKGemm, _d, _ptr, _ptr8
+from . import _st_plan
+from ._gemm_plan import _ptr, _ptr8
 from ._lib import check
+from ._st_plan import ACT_RELU, _align4, _BlockDesc  # noqa: F401  (_BlockDesc: the kernel tests build their own)
 
-ACT_NONE, ACT_RELU, ACT_LEAKY01 = 0, 1, _lib.ACT_LEAKY_RELU_01
-
-
-class _BlockDesc(ctypes.Structure):
-    """include/dib_st.h dib_st_block_desc: element offsets of one attention block's token-wise chain in the flat parameter buffer"""
-    _fields_ = [("o_w", ctypes.c_int64), ("o_b", ctypes.c_int64), ("ln1_g", ctypes.c_int64), ("ln1_b", ctypes.c_int64),
-                ("ln2_g", ctypes.c_int64), ("ln2_b", ctypes.c_int64), ("ff_w", ctypes.c_int64 * 3), ("ff_b", ctypes.c_int64 * 3),
-                ("n_ff", ctypes.c_int32), ("ff_width", ctypes.c_int32 * 3), ("D", ctypes.c_int32), ("HK", ctypes.c_int32),
-                ("eps", ctypes.c_float), ("act", ctypes.c_int32)]
-
-
-assert ctypes.sizeof(_BlockDesc) == 128
 LOSS_BCE_LOGITS = 0
 # Test switch: take train_step's collective branch even on a ONE-rank process group, so that the RCCL calls themselves run
 # on the single GPU the test box has (tests/_dp_gpu_st_worker.py).  A 1-rank sum all-reduce is the identity.
 _FORCE_DP_BRANCH = False
-
-
-def _align4(n: int) -> int:
-    return (n + 3) // 4 * 4
 
 
 def convert_to_per_particle_feature_set(particle_positions, types, number_particles_to_use=60):
@@ -148,32 +140,6 @@ def save_information_map(grids, path: str, masks=None, info_cmap: str = "gist_he
     plt.close(fig)
 
 
-class _SplitKGemm:
-    """A skinny product C[M, N] = A[M, K] @ W (N = the model width, 32; K = heads * key_dim = 1536) with FEW row tiles: the
-    output has ceil(M / 64) workgroups' worth of tiles and each would walk all of K with one tile of prefetch - at the
-    notebook's size (1600 tokens) 25 workgroups x 48 dependent k-tiles = 84 us for 0.16 GFLOP, the two slowest launches of
-    the whole step.  Here the contraction is cut into `ksplit` chunks that run as extra GROUPS of the same grouped launch
-    (one partial slab each), summed in a fixed order by dib_reduce_splits: deterministic, no new kernel."""
-
-    def __init__(self, gemm: "_Gemm", partial, partial_off, n, nslabs, out, out_off, mode: str = "store"):
-        """mode: "store" out = sum of the slabs; "add" out += sum (a residual branch's gradient joins the one already there:
-        one launch instead of reduce + add); "defer" no reduce here - the consumer sums the slabs itself
-        (dib_add_layernorm_fwd's b_slabs)."""
-        self.gemm, self.partial, self.partial_off, self.n, self.nslabs, self.out, self.out_off, self.mode = \
-            gemm, partial, partial_off, n, nslabs, out, out_off, mode
-
-    def upload(self, device):
-        self.gemm.upload(device)
-
-    def run(self, lib, stream):
-        self.gemm.run(lib, stream)
-        if self.mode == "defer":
-            return
-        fn = lib.dib_reduce_splits_add if self.mode == "add" else lib.dib_reduce_splits
-        check(fn(_ptr(self.partial, self.partial_off), self.n, self.nslabs, self.n, _ptr(self.out, self.out_off), stream),
-              "dib_reduce_splits")
-
-
 class SetTransformerDIB:
     """`particle_encoder` + `set_transformer` + `train_step` of the notebook as one device-resident object."""
 
@@ -183,9 +149,10 @@ class SetTransformerDIB:
                  ff_arch_per_block: Sequence[int] = (128, 32), final_processing_arch: Sequence[int] = (256,),
                  output_dimensionality: int = 1, logvar_initialization: float = -3.0, layer_norm_epsilon: float = 1e-3,
                  *, init_seed: int = 0, noise_seed: int = 0, device: Optional[str] = None, attention: str = "auto",
-                 attention_score_stash_bytes: int = 64 << 30, use_graphs: Optional[bool] = None):
-        """use_graphs: replay the whole training step (copy-in, ~190 launches, Adam, noise-step bump) as one captured hipGraph
-        per (batch, particles) shape - the notebook's own configuration, 32 neighbourhoods x 50 particles, is bound by launch
+                 attention_score_stash_bytes: int = 64 << 30, use_graphs: Optional[bool] = None,
+                 skinny_k_min_tokens: int = 1024):
+        """use_graphs: replay the whole training step (copy-in, its 38 launches at the notebook's size, Adam, noise-step bump)
+        as one captured hipGraph per (batch, particles) shape - the notebook's own configuration, 32 neighbourhoods x 50 particles, is bound by launch
         and dependency latency, not by arithmetic.  Default: the DIB_ENABLE_GRAPHS=1 opt-in shared with DistributedIBNet.fit.
         Single-process only (the data-parallel step has collectives between its launches).
         attention_score_stash_bytes: flash attention keeps the raw [P, P] score tiles of every block for the backward
@@ -195,7 +162,10 @@ class SetTransformerDIB:
         grouped GEMMs with the [P, P] probabilities stashed in HBM (any key_dim), "auto" (per batch shape, key_dim == 128):
         flash - since the round-2 rewrite of the attention kernels it is the faster path at every measured shape (ms/step flash
         vs gemm: 32 x 50: 3.08 / 4.14, 4 x 512: 4.29 / 4.88, 2 x 2048: 15.0 / 15.7, 4 x 4096: 77.2 / 100.5;
-        profiles/r02am_set_transformer_bench.txt, r02final2_set_transformer_bench.txt) and it needs no [P, P] stash in HBM; key_dim != 128: gemm."""
+        profiles/r02am_set_transformer_bench.txt, r02final2_set_transformer_bench.txt) and it needs no [P, P] stash in HBM; key_dim != 128: gemm.
+        skinny_k_min_tokens: token count from which the q / k / v projections and the context gradient run as streaming
+        skinny-K launches (same-box A/B, profiles/r03ad_*: 400 tokens +1.5 %, 1024 -1 %, 1600 -1.7 %, 2048 -5.7 %,
+        16 384 -1 % of the step)."""
         self._acquire_device(device)
         self.particle_feature_dimensions = int(particle_feature_dimensions)
         self.number_positional_encoding_frequencies = int(number_positional_encoding_frequencies)
@@ -216,9 +186,17 @@ class SetTransformerDIB:
             raise ValueError("attention='flash' needs key_dim == 128 (the notebook's value)")
         self.attention = attention
         self.attention_score_stash_bytes = int(attention_score_stash_bytes)
-        # token count from which the q / k / v projections and the context gradient run as streaming skinny-K launches
-        # (same-box A/B, profiles/r03ad_*: 400 tokens +1.5 %, 1024 -1 %, 1600 -1.7 %, 2048 -5.7 %, 16 384 -1 % of the step)
-        self.skinny_k_min_tokens = int(os.environ.get("DIB_SKINNY_K_MIN_TOKENS", "1024"))
+        self.skinny_k_min_tokens = int(skinny_k_min_tokens)
+        # A/B switches of the dispatch (_st_plan.decide reads them when it plans a shape: set them before the first step of
+        # that shape).  Each names a path that is taken where its kernels support the shape; off = the general path.
+        self.use_chain = True                   # the token-wise half of a block as one launch per direction (dib_st_chain_*)
+        self.defer_wgrads = True                # all blocks' weight gradients at the end of the backward, grouped by shape class
+        self.deferred_max_slabs = 8             # ... their row slabs over the tokens at most (each costs the optimizer a pass)
+        self.deferred_wgrad_target_wgs = 1536   # ... and the workgroups one of those launches aims at
+        self.encoder_row_tiles = True           # the particle encoder on the row-tile MLP kernels (dib_mlp_small_fwd / _bwd)
+        self.head_row_tiles = True              # the head's share of a training step as one launch (dib_mlp_small_head_step)
+        self.attention_proj = True              # q / k / v projections inside the attention forward (<= 64 particles)
+        self.attention_bwd_proj = True          # ... and their input gradient inside the attention backward
         self.attention_impl = "flash" if (attention == "flash" or (attention == "auto" and self.key_dim == 128)) else "gemm"
         assert self.bottleneck_dimension <= 256 and self.bottleneck_dimension % 4 == 0
         # ---- flat parameter layout (Keras creation order) ----
@@ -245,6 +223,9 @@ class SetTransformerDIB:
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=self.device)   # noise step of graph replays (uint32 bits)
         self._step = 0
         self.last = {}
+        self._unreduced: Optional[dict] = None   # the plan whose slabs loss_and_backward(reduce=False) left for the optimizer
+        self._sync: Optional[torch.Tensor] = None      # dib_reduce_adam_step's grid-sync words, allocated by its first call
+        self._info_ws: Optional[torch.Tensor] = None   # float64 workspace of the information estimators, grown on demand
 
     state_dtype = torch.float32   # parameters, gradients and Adam moments live on the device in the reference's own precision
 
@@ -339,371 +320,14 @@ class SetTransformerDIB:
         return c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _plan(self, B: int, P: int) -> dict:
+        """The step plan of a (batch, particles) shape - workspace map, descriptor tables, dispatch decisions
+        (_st_plan.build_step_plan) - from the LRU cache.  A plan holds the whole step workspace + the gradient slabs (166 MB at
+        4 x 4096): the few most recent shapes are kept (training batch, validation batch, a ragged tail)."""
         key = (B, P)
         if key in self._plans:
             self._plans[key] = self._plans.pop(key)   # most recently used last
             return self._plans[key]
-        D, H, K = self.bottleneck_dimension, self.number_heads_per_mha, self.key_dim
-        HK, T = H * K, B * P
-        ldS = _align4(P)
-        impl = self.attention_impl   # fixed by the constructor: flash for key_dim == 128 unless attention="gemm"
-        F0 = self.particle_feature_dimensions
-        pe_w = F0 * self.number_positional_encoding_frequencies
-        enc_units = self.particle_encoder_arch_spec + [2 * D]
-        ff = self.ff_arch_per_block
-        off: Dict[str, int] = {}
-        o = 0
-
-        def take(name, n):
-            nonlocal o
-            off[name] = o
-            o = _align4(o + int(n)) + 0
-            return off[name]
-
-        take("feats", T * F0)
-        take("pe", T * pe_w)
-        for l, u in enumerate(enc_units):
-            take(f"enc_h{l}", T * u)                # last one = enc_out (mu | raw logvar)
-        take("x0", T * D)                           # u = sampled embeddings
-        for b in range(self.number_attention_blocks):
-            for nm in ("q", "k", "v", "ctx"):
-                take(f"b{b}_{nm}", T * HK)
-            if impl == "gemm":
-                take(f"b{b}_S", B * H * P * ldS)    # attention probabilities (stashed for the backward)
-            else:
-                take(f"b{b}_lse", B * H * P)        # per-query log-sum-exp (the flash backward recomputes the rest)
-            take(f"b{b}_mha", T * D)
-            take(f"b{b}_xhat1", T * D); take(f"b{b}_rstd1", T); take(f"b{b}_h", T * D)
-            d = D
-            for l, u in enumerate(ff):
-                take(f"b{b}_ff{l}", T * u)
-            take(f"b{b}_xhat2", T * D); take(f"b{b}_rstd2", T); take(f"b{b}_x", T * D)
-        take("pool", B * D)
-        for l, u in enumerate(self.final_processing_arch):
-            take(f"fin{l}", B * u)
-        take("pred", B * self.output_dimensionality)
-        take("g_pred", B * self.output_dimensionality)
-        take("out3", 4)
-        take("kl_sum", 4)
-        # backward scratch (reused by every block)
-        for l, u in enumerate(self.final_processing_arch):
-            take(f"g_fin{l}", B * u)
-        take("g_pool", B * D)
-        # g_x / g_s: gradient w.r.t. a block's output / input, ping-ponging from block to block (no copy); g_a: both addends
-        # of LN2; g_z: feed-forward pre-activation; g_h: the feed-forward branch's gradient w.r.t. h
-        take("g_x", T * D); take("g_s", T * D); take("g_a", T * D); take("g_z", T * D); take("g_h", T * D)
-        for l, u in enumerate(ff[:-1]):
-            take(f"g_ff{l}", T * u)
-        for nm in ("q", "k", "v", "ctx"):
-            take(f"g_{nm}", T * HK)
-        if impl == "gemm":
-            take("g_S", B * H * P * ldS)
-        else:
-            take("attn_delta", int(self.lib.dib_attention_bwd_workspace_bytes(B, P, H)) // 4)   # delta + dQ key-block partials
-        for nm in ("q", "k", "v"):
-            take(f"g_x{nm}", T * D)
-        # split-K of the two skinny [T, heads*key_dim] x [heads*key_dim, D] products when there are few row tiles (_SplitKGemm)
-        ksplit, mt = 1, (T + 63) // 64
-        if mt < 128:
-            for cand in (8, 4, 2):
-                if HK % (cand * 32) == 0 and HK // cand >= 64:
-                    ksplit = cand
-                    break
-        if ksplit > 1:
-            take("ksplit_ws", 3 * ksplit * T * D)
-        for l, u in enumerate(enc_units):
-            take(f"g_enc_h{l}", T * u)
-        ln_ws = int(self.lib.dib_add_layernorm_bwd_workspace_bytes(T, D)) // 4
-        take("ln_ws", ln_ws)
-        take("kl_ws", int(self.lib.dib_token_kl_workspace_bytes(T, D)) // 4 + 4)
-        # the token-wise half of every block as one launch per direction (csrc/dib_st_chain.h) for up to 4096 tokens
-        chain_descs = []
-        if getattr(self, "use_chain", True) and len(ff) <= 3:
-            for b in range(self.number_attention_blocks):
-                pre = f"blk{b}_"
-                dsc = _BlockDesc()
-                dsc.o_w, dsc.o_b = self.offsets[pre + "o_w"], self.offsets[pre + "o_b"]
-                dsc.ln1_g, dsc.ln1_b = self.offsets[pre + "ln1_g"], self.offsets[pre + "ln1_b"]
-                dsc.ln2_g, dsc.ln2_b = self.offsets[pre + "ln2_g"], self.offsets[pre + "ln2_b"]
-                for l, u in enumerate(ff):
-                    dsc.ff_w[l], dsc.ff_b[l], dsc.ff_width[l] = self.offsets[pre + f"ff{l}_w"], self.offsets[pre + f"ff{l}_b"], u
-                dsc.n_ff, dsc.D, dsc.HK, dsc.eps, dsc.act = len(ff), D, HK, self.layer_norm_epsilon, ACT_RELU
-                chain_descs.append(dsc)
-            if not (chain_descs and all(self.lib.dib_st_chain_supported(ctypes.byref(dsc), T) for dsc in chain_descs)):
-                chain_descs = []
-        if chain_descs:
-            take("chain_ws", int(self.lib.dib_st_chain_workspace_bytes(T, D)) // 4)
-        # Deferred weight gradients (round 6): on the chain path every block keeps the operands of its weight gradients in
-        # buffers of its own - dL/d(feed-forward pre-activations), dL/dq|k|v, and the gradient of LN1's addends (slot 0 of
-        # b{b}_dx; slots 1.. are the split-K slabs of the q/k/v input gradient, so that ONE fixed-order sum over the slots is
-        # the gradient handed to the next block and slot 0 stays what the output projection's weight gradient contracts
-        # with) - and ALL blocks' weight gradients run at the end of the backward as one grouped launch per shape class
-        # (q/k/v: 3 x blocks groups of [D, HK]; output projection: [HK, D]; feed-forward) instead of 3 launches per block:
-        # at the notebook's size 18 launches of 7-18 us on a few dozen workgroups each become 3 that fill the chip.
-        defer = bool(chain_descs) and ksplit > 1 and bool(getattr(self, "defer_wgrads", True))
-        if defer:
-            for b in range(self.number_attention_blocks):
-                take(f"b{b}_g_z", T * D)
-                for l, u in enumerate(ff[:-1]):
-                    take(f"b{b}_g_ff{l}", T * u)
-                for nm in "qkv":
-                    take(f"b{b}_g_{nm}", T * HK)
-                take(f"b{b}_dx", (1 + max(3 * ksplit, H)) * T * D)   # slot 0 + split-K slabs, or + one slab per head (attn_bwd_proj)
-        gn = (lambda b, nm: f"b{b}_{nm}") if defer else (lambda b, nm: nm)   # per-block / shared gradient buffer names
-        take("loss_ws", int(self.lib.dib_loss_rows_workspace_bytes(B)) // 4 + 4)
-        ws = torch.zeros(o, dtype=torch.float32, device=self.device)
-        # flash attention, stash mode: one score-tile buffer per block, outside the fp32-indexed workspace (its own allocation:
-        # 3.2 GB per block at 4 x 4096); None = recompute mode
-        # It is allocated LAZILY by the first forward that a backward will follow (_ensure_stash): evaluation-only shapes
-        # (validation batches, the sampled second pass of fit) never own one.
-        stash = None
-        stash_block_bytes = int(self.lib.dib_attention_stash_bytes(B, P, H)) if impl == "flash" else 0
-
-        # weight-gradient target: contraction over T tokens is split into slabs when T is large (fixed-order reduce)
-        # (from 512 tokens up: with one slab the q/k/v and output-projection wgrads of the reference size, 1600 tokens, ran on
-        # 12-36 workgroups looping over all rows - 110-137 us each, the top entries of the first profile)
-        # (64-row slabs up to 2048 tokens: at 1600 tokens the 6 slabs of the T // 256 rule left the feed-forward wgrads on 6
-        # workgroups walking 9 dependent k-tiles each - 24 us per launch, 28 such launches per step)
-        # (deferred weight gradients: many groups per launch fill the chip with FEW splits, and every slab costs the optimizer's
-        # launch a pass over the whole gradient buffer - 25 slabs x 5.2 MB were 130 MB, 33 us of a 1.29 ms step at the notebook's
-        # size; `deferred_max_slabs`)
-        nsplit = max(1, min(int(getattr(self, "deferred_max_slabs", 8)) if defer else 32, T // 64))
-        rps = ((T + nsplit - 1) // nsplit + 31) // 32 * 32
-        nsplit = (T + rps - 1) // rps
-        slabs = torch.zeros(nsplit * self.n_alloc, dtype=torch.float32, device=self.device) if nsplit > 1 else None
-        gt = slabs if nsplit > 1 else self.grads
-        po = self.offsets
-
-        def dense_fwd(x, kin, w, b, y, kout, act, M):
-            return _Gemm(0, [_d(off[x], kin, po[w], kout, off[y], kout, M, kout, kin, bias_off=po[b])], ws, self.params, ws,
-                         bias=self.params, act=act)
-
-        def dense_dgrad(dy, kout, w, dx, kin, M, aux=None, act=0):
-            return _Gemm(1, [_d(off[dy], kout, po[w], kout, off[dx], kin, M, kin, kout,
-                                aux_off=off[aux] if aux else 0, ldaux=kin)], ws, self.params, ws,
-                         aux=ws if aux else None, act=act if aux else 0)
-
-        def dense_wgrad(x, kin, dy, kout, w, b, M, split=True):
-            ns, r = (nsplit, rps) if split else (1, max(M, 1))
-            return _Gemm(2, [_d(off[x], kin, off[dy], kout, po[w], kout, kin, kout, M, bias_off=po[b])], ws, ws, gt,
-                         bias_out=gt, nsplit=ns, rows_per_split=r, split_stride=self.n_alloc)
-
-        g: Dict[str, _Gemm] = {}
-        # particle encoder (shared by all particles): [T, 60] -> 128 -> 128 -> 64
-        kin, src = pe_w, "pe"
-        for l, u in enumerate(enc_units):
-            act = ACT_LEAKY01 if l < len(enc_units) - 1 else ACT_NONE
-            g[f"enc{l}_fwd"] = dense_fwd(src, kin, f"enc{l}_w", f"enc{l}_b", f"enc_h{l}", u, act, T)
-            g[f"enc{l}_wgrad"] = dense_wgrad(src, kin, f"g_enc_h{l}", u, f"enc{l}_w", f"enc{l}_b", T)
-            if l > 0:
-                g[f"enc{l}_dgrad"] = dense_dgrad(f"g_enc_h{l}", u, f"enc{l}_w", f"g_enc_h{l - 1}", kin, T, aux=f"enc_h{l - 1}",
-                                                 act=ACT_LEAKY01)
-            kin, src = u, f"enc_h{l}"
-        bh = [(b_, h_) for b_ in range(B) for h_ in range(H)]
-        dw_qkv, dw_o, dw_ff = [], [], []   # deferred weight gradients: descriptors of all blocks by shape class
-        for b in range(self.number_attention_blocks):
-            xin = "x0" if b == 0 else f"b{b - 1}_x"
-            pre = f"blk{b}_"
-            # q, k, v projections: 3 groups
-            qkv_descs = [_d(off[xin], D, po[pre + nm + "_w"], HK, off[f"b{b}_{nm}"], HK, T, HK, D, bias_off=po[pre + nm + "_b"])
-                         for nm in "qkv"]
-            # from skinny_k_min_tokens tokens up the projections out of the D-wide residual stream are store-bound streaming
-            # launches (dib_gemm_skinny_k); below, the tiled grouped GEMM
-            skinny = T >= self.skinny_k_min_tokens
-            mk = _SkinnyKGemm if skinny and _SkinnyKGemm.fits(0, qkv_descs) else _Gemm
-            g[f"b{b}_qkv_fwd"] = mk(0, qkv_descs, ws, self.params, ws, bias=self.params)
-            gemm_attn = impl == "gemm"
-            # scores S_bh = Q_bh K_bh^T (scale folded into the softmax)
-            if gemm_attn:
-                g[f"b{b}_qk"] = _Gemm(1, [_d(off[f"b{b}_q"] + bi * P * HK + hi * K, HK, off[f"b{b}_k"] + bi * P * HK + hi * K, HK,
-                                           off[f"b{b}_S"] + (bi * H + hi) * P * ldS, ldS, P, P, K) for bi, hi in bh], ws, ws, ws)
-            # ctx_bh = P_bh V_bh
-            if gemm_attn:
-                g[f"b{b}_pv"] = _Gemm(0, [_d(off[f"b{b}_S"] + (bi * H + hi) * P * ldS, ldS, off[f"b{b}_v"] + bi * P * HK + hi * K, HK,
-                                           off[f"b{b}_ctx"] + bi * P * HK + hi * K, HK, P, K, P) for bi, hi in bh], ws, ws, ws)
-            if ksplit > 1:
-                ck = HK // ksplit
-                g[f"b{b}_o_fwd"] = _SplitKGemm(
-                    _Gemm(0, [_d(off[f"b{b}_ctx"] + s_ * ck, HK, po[pre + "o_w"] + s_ * ck * D, D, off["ksplit_ws"] + s_ * T * D, D,
-                                 T, D, ck, bias_off=po[pre + "o_b"] if s_ == 0 else -1) for s_ in range(ksplit)],
-                          ws, self.params, ws, bias=self.params),
-                    ws, off["ksplit_ws"], T * D, ksplit, ws, off[f"b{b}_mha"], mode="defer")   # LN1 sums the slabs
-            else:
-                g[f"b{b}_o_fwd"] = dense_fwd(f"b{b}_ctx", HK, pre + "o_w", pre + "o_b", f"b{b}_mha", D, ACT_NONE, T)
-            d, src = D, f"b{b}_h"
-            for l, u in enumerate(ff):
-                g[f"b{b}_ff{l}_fwd"] = dense_fwd(src, d, pre + f"ff{l}_w", pre + f"ff{l}_b", f"b{b}_ff{l}", u, ACT_RELU, T)
-                d, src = u, f"b{b}_ff{l}"
-            # ---- backward ----
-            # feed-forward: g_z = dL/d(pre-activation of the last ff layer)
-            nff = len(ff)
-            gy, ky = "g_z", ff[-1]
-            for l in range(nff - 1, -1, -1):
-                kin_l = D if l == 0 else ff[l - 1]
-                src_l = f"b{b}_h" if l == 0 else f"b{b}_ff{l - 1}"
-                g[f"b{b}_ff{l}_wgrad"] = dense_wgrad(src_l, kin_l, gy, ky, pre + f"ff{l}_w", pre + f"ff{l}_b", T)
-                if l > 0:
-                    g[f"b{b}_ff{l}_dgrad"] = dense_dgrad(gy, ky, pre + f"ff{l}_w", f"g_ff{l - 1}", kin_l, T, aux=src_l, act=ACT_RELU)
-                    gy, ky = f"g_ff{l - 1}", kin_l
-                else:
-                    g[f"b{b}_ff0_dgrad"] = dense_dgrad(gy, ky, pre + "ff0_w", "g_h", D, T)
-            # attention output projection
-            gout = self._block_grad_names(b)[1]   # gradient w.r.t. the block's input x (= gradient of LN1's two addends)
-            if defer:
-                off[f"b{b}_gln1"] = off[f"b{b}_dx"]   # slot 0 of the block's dx region (alias)
-            g[f"b{b}_o_wgrad"] = dense_wgrad(f"b{b}_ctx", HK, f"b{b}_gln1" if defer else gout, D, pre + "o_w", pre + "o_b", T)
-            o_dgrad_descs = [_d(off[gout], D, po[pre + "o_w"], D, off["g_ctx"], HK, T, HK, D)]
-            mk = _SkinnyKGemm if skinny and _SkinnyKGemm.fits(1, o_dgrad_descs) else _Gemm
-            g[f"b{b}_o_dgrad"] = mk(1, o_dgrad_descs, ws, self.params, ws)
-            if gemm_attn:
-                g[f"b{b}_dv"] = _Gemm(2, [_d(off[f"b{b}_S"] + (bi * H + hi) * P * ldS, ldS, off["g_ctx"] + bi * P * HK + hi * K, HK,
-                                           off[gn(b, "g_v")] + bi * P * HK + hi * K, HK, P, K, P) for bi, hi in bh], ws, ws, ws,
-                                    nsplit=1, rows_per_split=max(P, 1))
-            if gemm_attn:
-                g[f"b{b}_dp"] = _Gemm(1, [_d(off["g_ctx"] + bi * P * HK + hi * K, HK, off[f"b{b}_v"] + bi * P * HK + hi * K, HK,
-                                           off["g_S"] + (bi * H + hi) * P * ldS, ldS, P, P, K) for bi, hi in bh], ws, ws, ws)
-            if gemm_attn:
-                g[f"b{b}_dq"] = _Gemm(0, [_d(off["g_S"] + (bi * H + hi) * P * ldS, ldS, off[f"b{b}_k"] + bi * P * HK + hi * K, HK,
-                                           off[gn(b, "g_q")] + bi * P * HK + hi * K, HK, P, K, P) for bi, hi in bh], ws, ws, ws)
-            if gemm_attn:
-                g[f"b{b}_dk"] = _Gemm(2, [_d(off["g_S"] + (bi * H + hi) * P * ldS, ldS, off[f"b{b}_q"] + bi * P * HK + hi * K, HK,
-                                           off[gn(b, "g_k")] + bi * P * HK + hi * K, HK, P, K, P) for bi, hi in bh], ws, ws, ws,
-                                    nsplit=1, rows_per_split=max(P, 1))
-            qkv_wgrad_descs = [_d(off[xin], D, off[gn(b, f"g_{nm}")], HK, po[pre + nm + "_w"], HK, D, HK, T, bias_off=po[pre + nm + "_b"])
-                               for nm in "qkv"]
-            g[f"b{b}_qkv_wgrad"] = _Gemm(2, qkv_wgrad_descs, ws, ws, gt, bias_out=gt,
-                                         nsplit=nsplit, rows_per_split=rps, split_stride=self.n_alloc)
-            if defer:
-                dw_qkv += qkv_wgrad_descs
-                dw_o.append(_d(off[f"b{b}_ctx"], HK, off[f"b{b}_gln1"], D, po[pre + "o_w"], D, HK, D, T, bias_off=po[pre + "o_b"]))
-            if chain_descs:
-                # the feed-forward layers' weight gradients in one grouped launch (dy = the chain backward's g_ff); the output
-                # projection's (dy = the gradient of LN1's addends = the block-input gradient buffer BEFORE the projections' dgrads
-                # are added) and q / k / v's keep their own launches
-                descs = []
-                for l in range(nff):
-                    kin_l, src_l = (D, f"b{b}_h") if l == 0 else (ff[l - 1], f"b{b}_ff{l - 1}")
-                    dy_l = gn(b, "g_z" if l == nff - 1 else f"g_ff{l}")
-                    descs.append(_d(off[src_l], kin_l, off[dy_l], ff[l], po[pre + f"ff{l}_w"], ff[l], kin_l, ff[l], T,
-                                    bias_off=po[pre + f"ff{l}_b"]))
-                # (one launch for ALL of them was tried: a grouped launch's grid is max-shape tiles x groups, and [1536, 32] next to
-                # [32, 1536] made it 21 600 mostly empty workgroups - 48 us; the feed-forward layers share a shape class)
-                g[f"b{b}_ff_wgrad"] = _Gemm(2, descs, ws, ws, gt, bias_out=gt, nsplit=nsplit, rows_per_split=rps,
-                                            split_stride=self.n_alloc)
-                if defer:
-                    dw_ff += descs
-            if defer:
-                # the slabs land behind the LN1-addend gradient in the block's own region; the sum over all slots is taken by
-                # the consumer: the previous block's chain launch sums them as it loads its tile (dib_st_chain_bwd g_out_slabs),
-                # block 0's go through one reduce launch into the buffer the bottleneck's backward reads
-                ck = HK // ksplit
-                g[f"b{b}_qkv_dgrad"] = _SplitKGemm(
-                    _Gemm(1, [_d(off[f"b{b}_g_{nm}"] + s_ * ck, HK, po[pre + nm + "_w"] + s_ * ck, HK,
-                                 off[f"b{b}_dx"] + (1 + i_ * ksplit + s_) * T * D, D, T, D, ck)
-                              for i_, nm in enumerate("qkv") for s_ in range(ksplit)], ws, self.params, ws),
-                    ws, off[f"b{b}_dx"], T * D, 1 + 3 * ksplit, ws, off[gout], mode="store" if b == 0 else "defer")
-            elif ksplit > 1:   # 3 projections x ksplit chunks -> 3 * ksplit slabs, summed straight into g_xq (= g_xq + g_xk + g_xv)
-                ck = HK // ksplit
-                g[f"b{b}_qkv_dgrad"] = _SplitKGemm(
-                    _Gemm(1, [_d(off[f"g_{nm}"] + s_ * ck, HK, po[pre + nm + "_w"] + s_ * ck, HK,
-                                 off["ksplit_ws"] + (i_ * ksplit + s_) * T * D, D, T, D, ck)
-                              for i_, nm in enumerate("qkv") for s_ in range(ksplit)], ws, self.params, ws),
-                    ws, off["ksplit_ws"], T * D, 3 * ksplit, ws, off[self._block_grad_names(b)[1]], mode="add")
-            else:
-                g[f"b{b}_qkv_dgrad"] = _Gemm(1, [_d(off[f"g_{nm}"], HK, po[pre + nm + "_w"], HK, off[f"g_x{nm}"], D, T, D, HK)
-                                                 for nm in "qkv"], ws, self.params, ws)
-        # head: pooled [B, D] -> Dense(256, LeakyReLU(0.1)) -> Dense(out)
-        d, src = D, "pool"
-        for l, u in enumerate(self.final_processing_arch):
-            g[f"fin{l}_fwd"] = dense_fwd(src, d, f"fin{l}_w", f"fin{l}_b", f"fin{l}", u, ACT_LEAKY01, B)
-            d, src = u, f"fin{l}"
-        g["out_fwd"] = dense_fwd(src, d, "out_w", "out_b", "pred", self.output_dimensionality, ACT_NONE, B)
-        g["out_wgrad"] = dense_wgrad(src, d, "g_pred", self.output_dimensionality, "out_w", "out_b", B, split=False)
-        nfin = len(self.final_processing_arch)
-        if nfin:
-            g["out_dgrad"] = dense_dgrad("g_pred", self.output_dimensionality, "out_w", f"g_fin{nfin - 1}", d, B,
-                                         aux=f"fin{nfin - 1}", act=ACT_LEAKY01)
-        else:
-            g["out_dgrad"] = dense_dgrad("g_pred", self.output_dimensionality, "out_w", "g_pool", d, B)
-        for l in range(nfin - 1, -1, -1):
-            kin_l = D if l == 0 else self.final_processing_arch[l - 1]
-            src_l = "pool" if l == 0 else f"fin{l - 1}"
-            u = self.final_processing_arch[l]
-            g[f"fin{l}_wgrad"] = dense_wgrad(src_l, kin_l, f"g_fin{l}", u, f"fin{l}_w", f"fin{l}_b", B, split=False)
-            if l > 0:
-                g[f"fin{l}_dgrad"] = dense_dgrad(f"g_fin{l}", u, f"fin{l}_w", f"g_fin{l - 1}", kin_l, B, aux=src_l, act=ACT_LEAKY01)
-            else:
-                g["fin0_dgrad"] = dense_dgrad(f"g_fin{l}", u, "fin0_w", "g_pool", D, B)
-        # the particle encoder (PositionalEncoding -> Dense(LeakyReLU(0.1))* -> Dense) on the row-tile MLP kernels for up to 2048
-        # tokens: one launch forward (encoding included), one for the dgrad chain, instead of 4 + 2
-        enc_mlp = None
-        if getattr(self, "encoder_row_tiles", True) and 2 <= len(enc_units) <= 4:
-            from .dense import _MlpDesc
-            dsc = _MlpDesc()
-            for l, u in enumerate(enc_units):
-                dsc.w_off[l], dsc.b_off[l], dsc.width[l] = po[f"enc{l}_w"], po[f"enc{l}_b"], u
-            dsc.n_hidden, dsc.in_dim, dsc.n_freq, dsc.act = len(enc_units) - 1, F0, self.number_positional_encoding_frequencies, ACT_LEAKY01
-            if self.lib.dib_mlp_small_supported(ctypes.byref(dsc), T):
-                nh = len(enc_units) - 1
-                hp = lambda pre: (c_void_p * 3)(*[_ptr(ws, off[f"{pre}{l}"]).value if l < nh else None for l in range(3)])
-                enc_mlp = dict(desc=dsc, h=hp("enc_h"), g=hp("g_enc_h"))
-        # the head (pooled neighbourhood -> Dense(LeakyReLU(0.1))* -> Dense(1) -> BCE) as ONE launch for its whole share of a training
-        # step (dib_mlp_small_head_step): forward, loss, gradient of the logit, dgrad chain, the output layer's gradient
-        head_mlp = None
-        if getattr(self, "head_row_tiles", True) and self.output_dimensionality == 1 and 1 <= nfin <= 3:
-            from .dense import _MlpDesc
-            dsc = _MlpDesc()
-            for l, u in enumerate(self.final_processing_arch):
-                dsc.w_off[l], dsc.b_off[l], dsc.width[l] = po[f"fin{l}_w"], po[f"fin{l}_b"], u
-            dsc.w_off[nfin], dsc.b_off[nfin], dsc.width[nfin] = po["out_w"], po["out_b"], 1
-            dsc.n_hidden, dsc.in_dim, dsc.n_freq, dsc.act = nfin, D, 1, ACT_LEAKY01
-            if self.lib.dib_mlp_small_head_supported(ctypes.byref(dsc), B):
-                hp = lambda pre: (c_void_p * 3)(*[_ptr(ws, off[f"{pre}{l}"]).value if l < nfin else None for l in range(3)])
-                head_ws = torch.zeros(int(self.lib.dib_mlp_small_head_workspace_bytes(ctypes.byref(dsc), B)) // 4 + 4,
-                                      dtype=torch.float32, device=self.device)
-                head_mlp = dict(desc=dsc, h=hp("fin"), g=hp("g_fin"), ws=head_ws)
-        deferred = []
-        if defer:
-            # the particle encoder's weight gradients contract over the same T tokens and fit the feed-forward class's tiles:
-            # three more groups of that launch instead of three launches; the head's (contraction over the B neighbourhoods)
-            # become one grouped launch
-            dw_ff += [dict(zip(DESC.names, g[f"enc{l}_wgrad"].host[0])) for l in range(len(enc_units))]
-            g["head_wgrads"] = _Gemm(2, [dict(zip(DESC.names, g[k].host[0])) for k in
-                                         ([] if head_mlp is not None else ["out_wgrad"]) + [f"fin{l}_wgrad" for l in range(nfin)]],
-                                     ws, ws, gt, bias_out=gt, nsplit=1, rows_per_split=max(B, 1), split_stride=self.n_alloc)
-            # one grouped launch per shape class.  A grouped launch's grid is (splits, tiles of the LARGEST group shape, groups):
-            # the split count of each class is chosen so that its workgroups make about `deferred_wgrad_target_wgs` - many
-            # groups need few, long splits (1536: the best of 384 / 512 / 768 / 1024 / 1536 at the notebook's size, 1.335 ...
-            # 1.319 ms per step, profiles/r06b_set_transformer_deferred_wgrads_ab.txt; 2048 and 3072 no better, r06c); slabs
-            # beyond a launch's count are never written and stay zero (the slab buffer is zero-initialised and every launch
-            # always writes the same slabs)
-            target = int(getattr(self, "deferred_wgrad_target_wgs", 1536))
-            for name, descs, (tm, tn) in (("dw_qkv", dw_qkv, (64, 128)), ("dw_o", dw_o, (128, 64)), ("dw_ff", dw_ff, (128, 128))):
-                mm, nn = max(d["M"] for d in descs), max(d["N"] for d in descs)
-                tiles = len(descs) * ((mm + tm - 1) // tm) * ((nn + tn - 1) // tn)
-                ns = max(1, min(nsplit, int(round(target / tiles))))
-                r = ((T + ns - 1) // ns + 63) // 64 * 64
-                ns = (T + r - 1) // r
-                g[name] = _Gemm(2, descs, ws, ws, gt, bias_out=gt, nsplit=ns, rows_per_split=r, split_stride=self.n_alloc)
-                deferred.append(name)
-        for gg in g.values():
-            gg.upload(self.device)
-        plan = dict(impl=impl, B=B, P=P, T=T, ldS=ldS, off=off, ws=ws, g=g, nsplit=nsplit, slabs=slabs, gt=gt, pe_w=pe_w,
-                    enc_units=enc_units, stash=stash, stash_block_bytes=stash_block_bytes, stash_denied=None, ksplit=ksplit,
-                    chain=chain_descs, deferred_wgrads=deferred, enc_mlp=enc_mlp, head_mlp=head_mlp,
-                    # <= 64 particles: the q / k / v projections inside the attention forward (dib_attention_fwd_proj)
-                    attn_proj=bool(impl == "flash" and getattr(self, "attention_proj", True)
-                                   and self.lib.dib_attention_fwd_proj_supported(P, K, D)),
-                    # ... and their input gradient inside the attention backward (one slab per head behind the LN1-addend
-                    # gradient; needs the per-block dx regions of the deferred mode and the 8-wave kernel)
-                    attn_bwd_proj=bool(defer and impl == "flash" and getattr(self, "attention_bwd_proj", True)
-                                       and self.lib.dib_attention_fwd_proj_supported(P, K, D)
-                                       and _lib.get_tuning("attn_small_bwd_waves") >= 8),
-                    qkv_off=[((ctypes.c_int64 * 3)(*[po[f"blk{b}_{nm}_w"] for nm in "qkv"]),
-                              (ctypes.c_int64 * 3)(*[po[f"blk{b}_{nm}_b"] for nm in "qkv"]))
-                             for b in range(self.number_attention_blocks)])
-        # a plan holds the whole step workspace + the gradient slabs (166 MB at 4 x 4096): keep the few most recent shapes
-        # (training batch, validation batch, a ragged tail), evict least recently used beyond that
+        plan = _st_plan.build_step_plan(self, B, P)
         step_keys = [k for k in self._plans if k[0] != "enc" and k not in self._graphs]   # a captured graph pins its plan
         if len(step_keys) >= self.max_step_plans:
             self._plans.pop(step_keys[0])
@@ -743,11 +367,10 @@ class SetTransformerDIB:
         pl["stash"] = bufs
         return True
 
-    def _block_grad_names(self, b: int):
-        """(buffer holding dL/d(output of block b), buffer receiving dL/d(input of block b)): "g_x" and "g_s" alternate from
-        block to block in backward order, so a block's result is the next block's input without a copy."""
-        k = self.number_attention_blocks - 1 - b
-        return ("g_x", "g_s") if k % 2 == 0 else ("g_s", "g_x")
+    def _f32(self, a, to_device: bool = True) -> torch.Tensor:
+        """array or tensor -> float32 tensor on the model's device (to_device=False: a tensor stays what and where it is)"""
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+        return t.to(device=self.device, dtype=torch.float32) if to_device else t
 
     def _view(self, plan, name, *shape):
         o = plan["off"][name]
@@ -769,8 +392,7 @@ class SetTransformerDIB:
         sample (treated as mu + sigma * eps with its implied eps held fixed: the reparameterised gradient of that sample), or
         the deterministic forward (x0 = mu: the term vanishes).  (Round 2 regenerated the library's eps in the backward, which
         was silently wrong for the last two - advisor finding.)"""
-        x = batch_inp if isinstance(batch_inp, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(batch_inp, dtype=np.float32))
-        x = x.to(device=self.device, dtype=torch.float32).contiguous()
+        x = self._f32(batch_inp).contiguous()
         B, P, F0 = x.shape
         assert F0 == self.particle_feature_dimensions
         pl = self._plan(B, P)
@@ -794,8 +416,7 @@ class SetTransformerDIB:
                                            int(row0), 1 if deterministic else 0, _ptr(ws, off["x0"]),
                                            _ptr(ws, off["kl_sum"]), _ptr(ws, off["kl_ws"]), st), "dib_token_reparam_kl_fwd")
         if embs_reparam is not None:
-            er = embs_reparam if isinstance(embs_reparam, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(embs_reparam, dtype=np.float32))
-            self._view(pl, "x0", T, D).copy_(er.to(device=self.device, dtype=torch.float32).reshape(T, D))
+            self._view(pl, "x0", T, D).copy_(self._f32(embs_reparam).reshape(T, D))
         scale = 1.0 / math.sqrt(self.key_dim)
         H = self.number_heads_per_mha
         for b in range(self.number_attention_blocks):
@@ -861,8 +482,7 @@ class SetTransformerDIB:
         B, P, T = self.last["B"], self.last["P"], pl["T"]
         lib, st, ws, off, g = self.lib, self._stream(), pl["ws"], pl["off"], pl["g"]
         D, H = self.bottleneck_dimension, self.number_heads_per_mha
-        y = is_loci if isinstance(is_loci, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(is_loci, dtype=np.float32))
-        y = y.to(device=self.device, dtype=torch.float32).reshape(B, -1).contiguous()
+        y = self._f32(is_loci).reshape(B, -1).contiguous()
         inv = 1.0 / B if inv_global_batch is None else float(inv_global_batch)
         gt = pl["gt"]
         if pl["nsplit"] == 1:
@@ -899,26 +519,26 @@ class SetTransformerDIB:
         nff = len(self.ff_arch_per_block)
         for b in range(self.number_attention_blocks - 1, -1, -1):
             pre = f"blk{b}_"
-            gin, gout = self._block_grad_names(b)
+            gin, gout = _st_plan.block_grad_names(self.number_attention_blocks, b)
             if pl["chain"]:
                 # LN2 backward -> feed-forward dgrads -> LN1 backward -> output-projection dgrad in one launch; then the attention
                 # backward, ONE grouped launch for the block's weight gradients, and the projections' dgrads (added to gout)
-                defer = bool(pl["deferred_wgrads"])   # the block's weight-gradient operands stay in buffers of its own
-                gb = (lambda nm: f"b{b}_{nm}") if defer else (lambda nm: nm)
+                # (deferred weight gradients, dw: the block's weight-gradient operands stay in buffers of its own)
+                gq, gk, gv = pl["grad_names"][b]["qkv"]
                 ffp = (c_void_p * 3)(*[_ptr(ws, off[f"b{b}_ff{l}"]) for l in range(nff)])
-                gfp = (c_void_p * 3)(*[_ptr(ws, off[gb("g_z" if l == nff - 1 else f"g_ff{l}")]) for l in range(nff)])
+                gfp = (c_void_p * 3)(*[_ptr(ws, off[nm]) for nm in pl["grad_names"][b]["ff"]])
                 # deferred: the gradient of this block's output is [LN1-addend gradient | q/k/v input-gradient slabs] of the
                 # NEXT block, summed by the kernel as it loads its tile; the last block's comes from the pooling backward
-                from_slabs = defer and b + 1 < self.number_attention_blocks
+                from_slabs = dw and b + 1 < self.number_attention_blocks
                 check(lib.dib_st_chain_bwd(ctypes.byref(pl["chain"][b]), T, _ptr(self.params),
                                            _ptr(ws, off[f"b{b + 1}_dx"] if from_slabs else off[gin]),
                                            (1 + (H if pl["attn_bwd_proj"] else 3 * pl["ksplit"])) if from_slabs else 1,
                                            T * D if from_slabs else 0,
                                            _ptr(ws, off[f"b{b}_xhat2"]), _ptr(ws, off[f"b{b}_rstd2"]), ffp,
                                            _ptr(ws, off[f"b{b}_xhat1"]), _ptr(ws, off[f"b{b}_rstd1"]), gfp,
-                                           _ptr(ws, off[f"b{b}_gln1" if defer else gout]),
+                                           _ptr(ws, off[f"b{b}_gln1" if dw else gout]),
                                            _ptr(ws, off["g_ctx"]), _ptr(gt), _ptr(ws, off["chain_ws"]), st), "dib_st_chain_bwd")
-                if not defer:
+                if not dw:
                     g[f"b{b}_ff_wgrad"].run(lib, st)
                     g[f"b{b}_o_wgrad"].run(lib, st)
                 if pl["attn_bwd_proj"]:
@@ -926,15 +546,15 @@ class SetTransformerDIB:
                     HK = H * self.key_dim
                     check(lib.dib_attention_bwd_proj(_ptr(ws, off[f"b{b}_q"]), _ptr(ws, off[f"b{b}_k"]), _ptr(ws, off[f"b{b}_v"]),
                                                      _ptr(ws, off["g_ctx"]), _ptr(ws, off[f"b{b}_lse"]), B, P, H, self.key_dim, D, HK, scale,
-                                                     _ptr(ws, off[gb("g_q")]), _ptr(ws, off[gb("g_k")]), _ptr(ws, off[gb("g_v")]),
+                                                     _ptr(ws, off[gq]), _ptr(ws, off[gk]), _ptr(ws, off[gv]),
                                                      _ptr(self.params), pl["qkv_off"][b][0], _ptr(ws, off[f"b{b}_dx"]), T * D, st),
                           "dib_attention_bwd_proj")
                     if b == 0:   # block 0's total goes to the buffer the bottleneck's backward reads
                         check(lib.dib_reduce_splits(_ptr(ws, off["b0_dx"]), T * D, 1 + H, T * D, _ptr(ws, off[gout]), st),
                               "dib_reduce_splits")
                     continue
-                self._attention_backward(pl, b, B, P, H, scale, *(gb(f"g_{nm}") for nm in "qkv"))
-                if not defer:
+                self._attention_backward(pl, b, B, P, H, scale, gq, gk, gv)
+                if not dw:
                     g[f"b{b}_qkv_wgrad"].run(lib, st)
                 g[f"b{b}_qkv_dgrad"].run(lib, st)
                 if pl["ksplit"] == 1:
@@ -1016,8 +636,8 @@ class SetTransformerDIB:
 
     def adam_step(self, beta_1=0.9, beta_2=0.999, epsilon=1e-7, fused_reduce: bool = False) -> None:
         if fused_reduce and self.n_alloc % 4 == 0:   # slab reduce + Keras-Adam + step-count bump in one launch
-            pl = getattr(self, "_unreduced", None)
-            if getattr(self, "_sync", None) is None:
+            pl = self._unreduced
+            if self._sync is None:
                 self._sync = torch.zeros(_lib.SYNC_WORDS, dtype=torch.int32, device=self.device)
             check(self.lib.dib_reduce_adam_step(_ptr(pl["slabs"]) if pl is not None else None, pl["nsplit"] if pl is not None else 0,
                                                 self.n_alloc, _ptr(self.params), _ptr(self.grads), _ptr(self.adam_m), _ptr(self.adam_v),
@@ -1025,7 +645,7 @@ class SetTransformerDIB:
                                                 _ptr(self._sync), self._stream()), "dib_reduce_adam_step")
             self._unreduced = None
             return
-        pl = getattr(self, "_unreduced", None)
+        pl = self._unreduced
         if pl is not None:   # (a deferred reduce that the fused path could not take)
             check(self.lib.dib_reduce_splits(_ptr(pl["slabs"]), self.n_alloc, pl["nsplit"], self.n_alloc, _ptr(self.grads),
                                              self._stream()), "dib_reduce_splits")
@@ -1083,15 +703,14 @@ class SetTransformerDIB:
         that changes between replays (beta, learning rate, Adam t, the noise step) already lives in device memory.  The
         eager warm-up runs exactly the captured sequence (module loads / hipFuncSetAttribute outside the capture) and every
         piece of state it touches is restored.  Same launches in the same order as the eager step: bit-identical results."""
-        x = batch_inp if isinstance(batch_inp, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(batch_inp, dtype=np.float32))
-        y = is_loci if isinstance(is_loci, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(is_loci, dtype=np.float32))
+        x, y = self._f32(batch_inp), self._f32(is_loci)
         B, P = int(x.shape[0]), int(x.shape[1])
         g = self._graphs.get((B, P))
         if g is None:
             xs = torch.zeros((B, P, self.particle_feature_dimensions), dtype=torch.float32, device=self.device)
             ys = torch.zeros((B, self.output_dimensionality), dtype=torch.float32, device=self.device)
-            xs.copy_(x.to(self.device).reshape(xs.shape))
-            ys.copy_(y.to(self.device).reshape(ys.shape))
+            xs.copy_(x.reshape(xs.shape))
+            ys.copy_(y.reshape(ys.shape))
             while len(self._graphs) >= self.max_graphs:   # oldest captured shape first: its plan (and stash) becomes evictable
                 torch.cuda.synchronize(self.device)      # no replay may be in flight when a graph object dies
                 self._graphs.pop(next(iter(self._graphs)))
@@ -1119,8 +738,8 @@ class SetTransformerDIB:
                 raise
             g = self._graphs[(B, P)] = dict(graph=graph, xs=xs, ys=ys, last=dict(self.last))
         else:
-            g["xs"].copy_(x.to(self.device).reshape(g["xs"].shape))
-            g["ys"].copy_(y.to(self.device).reshape(g["ys"].shape))
+            g["xs"].copy_(x.reshape(g["xs"].shape))
+            g["ys"].copy_(y.reshape(g["ys"].shape))
         self._set_step_dev(self._step)
         g["graph"].replay()
         self._step += 1
@@ -1131,8 +750,7 @@ class SetTransformerDIB:
         pl = self.last["plan"]
         B = self.last["B"]
         inv = 1.0 / B if inv_global_batch is None else float(inv_global_batch)
-        y = is_loci if isinstance(is_loci, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(is_loci, dtype=np.float32))
-        y = y.to(device=self.device, dtype=torch.float32).reshape(B, -1).contiguous()
+        y = self._f32(is_loci).reshape(B, -1).contiguous()
         ws, off = pl["ws"], pl["off"]
         check(self.lib.dib_loss_rows(LOSS_BCE_LOGITS, _ptr(ws, off["pred"]), self.output_dimensionality, _ptr(y), y.stride(0), B,
                                      inv, _ptr(ws, off["g_pred"]), _ptr(ws, off["out3"]), _ptr(ws, off["loss_ws"]),
@@ -1144,8 +762,7 @@ class SetTransformerDIB:
     # ---- the notebook's evaluation helpers ---------------------------------------------------------------------------------
     def particle_encoder(self, feats) -> torch.Tensor:
         """particle_encoder(features): [..., particle_feature_dimensions] -> [..., 2 * bottleneck] (mu | raw logvar)."""
-        x = feats if isinstance(feats, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(feats, dtype=np.float32))
-        x = x.to(device=self.device, dtype=torch.float32)
+        x = self._f32(feats)
         lead = x.shape[:-1]
         x = x.reshape(-1, self.particle_feature_dimensions).contiguous()
         T, F0 = x.shape[0], self.particle_feature_dimensions
@@ -1161,31 +778,14 @@ class SetTransformerDIB:
         return ws[o: o + T * E2].view(T, E2).clone().view(*lead, E2)
 
     def _encoder_plan(self, T: int) -> dict:
-        """Encoder-only workspace + GEMM descriptors for `particle_encoder` on T particles (no attention buffers)."""
+        """Encoder-only plan behind `particle_encoder` (_st_plan.build_encoder_plan); at most a few are kept (evaluation
+        batches come in a handful of sizes)."""
         key = ("enc", T)
-        if key in self._plans:
-            return self._plans[key]
-        F0 = self.particle_feature_dimensions
-        pe_w = F0 * self.number_positional_encoding_frequencies
-        units = self.particle_encoder_arch_spec + [2 * self.bottleneck_dimension]
-        off, o = {}, 0
-        for name, n in [("feats", T * F0), ("pe", T * pe_w)] + [(f"enc_h{l}", T * u) for l, u in enumerate(units)]:
-            off[name] = o
-            o = _align4(o + n)
-        ws = torch.zeros(o, dtype=torch.float32, device=self.device)
-        gs, kin, src = [], pe_w, "pe"
-        for l, u in enumerate(units):
-            act = ACT_LEAKY01 if l < len(units) - 1 else ACT_NONE
-            gs.append(_Gemm(0, [_d(off[src], kin, self.offsets[f"enc{l}_w"], u, off[f"enc_h{l}"], u, T, u, kin,
-                                   bias_off=self.offsets[f"enc{l}_b"])], ws, self.params, ws, bias=self.params, act=act))
-            kin, src = u, f"enc_h{l}"
-        for gg in gs:
-            gg.upload(self.device)
-        # keep at most a few encoder plans (evaluation batches come in a handful of sizes)
-        enc_keys = [k for k in self._plans if k[0] == "enc"]
-        if len(enc_keys) >= 4:
-            self._plans.pop(enc_keys[0])
-        self._plans[key] = dict(ws=ws, off=off, g=gs)
+        if key not in self._plans:
+            enc_keys = [k for k in self._plans if k[0] == "enc"]
+            if len(enc_keys) >= 4:
+                self._plans.pop(enc_keys[0])
+            self._plans[key] = _st_plan.build_encoder_plan(self, T)
         return self._plans[key]
 
     def probe_info_bounds(self, probe_features, data_features, seed: int = 0, step: int = 0, return_samples: bool = False):
@@ -1229,9 +829,7 @@ class SetTransformerDIB:
     # dib_mi_sandwich_batched, csrc/dib_st_info.h) --------------------------------------------------------------------------------
     def _val_table(self, particle_features_val):
         """(particle_encoder outputs of every validation particle [N_val * P, 2E] on the device, N_val, P)."""
-        xv = particle_features_val
-        if not isinstance(xv, torch.Tensor):
-            xv = torch.from_numpy(np.ascontiguousarray(xv, dtype=np.float32))
+        xv = self._f32(particle_features_val, to_device=False)   # (particle_encoder moves it)
         if xv.dim() != 3 or xv.shape[-1] != self.particle_feature_dimensions:
             raise ValueError(f"particle_features_val must be [neighbourhoods, particles, {self.particle_feature_dimensions}], got "
                              f"{tuple(xv.shape)}")
@@ -1240,7 +838,7 @@ class SetTransformerDIB:
         return enc, n_val, P
 
     def _f64_workspace(self, nbytes: int) -> torch.Tensor:
-        ws = getattr(self, "_info_ws", None)
+        ws = self._info_ws
         if ws is None or ws.numel() * 8 < nbytes:
             ws = self._info_ws = torch.empty(max(int(nbytes) // 8 + 2, 2), dtype=torch.float64, device=self.device)
         return ws
