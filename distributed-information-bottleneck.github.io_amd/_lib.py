@@ -18,13 +18,19 @@ LIB_PATH = os.path.join(_HERE, "libdib_hip.so")
 # Kernel A/B experiments (tools/ab_bench.sh) point DIB_LIB_PATH at a variant build (exp/lib_TAG.so); the product artefact is
 # never overwritten.  A set-but-missing path is an error, not a silent return to the product library.
 LIB_OVERRIDE = os.environ.get("DIB_LIB_PATH") or None
-INCLUDE = os.path.join(os.path.dirname(_HERE), "include", "dib_hip.h")
-INCLUDE_ST = os.path.join(os.path.dirname(_HERE), "include", "dib_st.h")
-INCLUDE_MEASURE = os.path.join(os.path.dirname(_HERE), "include", "dib_measure.h")
-INCLUDE_CIRCUIT = os.path.join(os.path.dirname(_HERE), "include", "dib_circuit.h")
-INCLUDE_PARTITION = os.path.join(os.path.dirname(_HERE), "include", "dib_partition.h")
-SOURCES = ["dib_api.hip", "dib_gemm.h", "dib_elementwise.h", "dib_common.h", "dib_fused.h", "dib_tail.h", "dib_small.h", "dib_st_chain.h", "dib_st.h", "dib_attn.h", "dib_attn_small.h", "dib_infonce_mfma.h",
-           "dib_measure.h", "dib_circuit.h", "dib_partition.h", INCLUDE_ST, INCLUDE_MEASURE, INCLUDE_CIRCUIT, INCLUDE_PARTITION]
+INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
+
+
+def _sources() -> list:
+    """Every file the one translation unit (csrc/dib_api.hip) can include: it, the kernel headers and the host fragments under
+    csrc/, and the public headers.  Read from the directories, so a new header needs no registration here.  (csrc/dib_ctw.cpp is
+    ctw.py's own build.)"""
+    out = []
+    for root, _, names in os.walk(CSRC):
+        out += [os.path.join(root, n) for n in names if n.endswith((".h", ".hip"))]
+    out += [os.path.join(INCLUDE_DIR, n) for n in os.listdir(INCLUDE_DIR) if n.endswith(".h")]
+    return sorted(out)
+
 
 # error codes (include/dib_hip.h)
 DIB_OK = 0
@@ -56,11 +62,7 @@ def _stale() -> bool:
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    for s in SOURCES + [INCLUDE]:
-        p = s if os.path.isabs(s) else os.path.join(CSRC, s)
-        if os.path.exists(p) and os.path.getmtime(p) > t:
-            return True
-    return False
+    return any(os.path.getmtime(p) > t for p in _sources())
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:

@@ -1,0 +1,259 @@
+// host/small.h - the row-tile integration kernel (csrc/dib_small.h): cluster sizing, the layout's launches, the plain-MLP entry
+// points (include/dib_hip.h dib_mlp_small_*) and the companion protocol that pairs the two in one grid.
+
+// A second, independent network for the NEXT dib_small_integration_kernel launch of this thread to carry in its grid
+// (dib_integration_fwd_and_mlp_fwd / dib_backward_and_mlp_bwd arm it; whoever armed it launches it alone if nobody took it).
+struct SmallCompanion { DibSmallIntArgs args; size_t lds = 0; bool armed = false; };
+static thread_local SmallCompanion t_companion;
+
+// workgroups per row tile of a row-tile network launch (dib_small.h "cluster mode"; 1 = the single-workgroup kernel): "int_cluster"
+// while the launch stays within "int_cluster_wgs" workgroups, the network's hidden layers hold at least "int_cluster_min_weights"
+// weights (below that a layer is a few microseconds on one CU and the exchanges cost more than they save) and the wider exchange
+// buffer fits the LDS
+static int small_cluster_size(const DibSmallIntArgs& a, size_t lds_bytes, int other_wgs = 0) {
+  int cl = std::min(knobs().int_cluster, DIB_SMALL_CL_MAX);
+  const int budget = std::min(knobs().int_cluster_wgs, device_cus());   // one workgroup per CU (141 KB of LDS each)
+  // more row tiles: 4 per tile instead of 8 while the launch (with the other network of a paired grid: other_wgs) stays within the
+  // budget - every workgroup must be resident for the networks to run side by side; 2 per tile measured no gain
+  // (profiles/r06u_int_cluster_sweep.txt)
+  while (cl > 4 && small_tiles(a.batch) * cl + other_wgs > budget) cl >>= 1;
+  if (cl <= 1 || small_tiles(a.batch) * cl + other_wgs > budget || lds_bytes > kSmallMaxLds) return 1;
+  if (a.mode & (DIB_SMALL_INT_HEAD_REDUCE)) return 1;   // (its last-arriver reduce counts workgroups, not tiles)
+  long long weights = 0;
+  for (int i = 0, k = a.K0; i < a.n_hidden; k = a.width[i], ++i) weights += (long long)k * a.width[i];
+  return weights >= knobs().int_cluster_min_weights ? cl : 1;
+}
+
+// one launch of dib_small_integration_kernel; `mode` = DIB_SMALL_INT_* bits.  Head arguments may be null / 0 without a head.
+static int small_integration(dib_layout* l, const dib_layout::WsMap& m, float* w, int batch, const float* params, int mode,
+                             int loss_kind, const float* y, int64_t ldy, const int32_t* row_idx, int64_t row0, float inv_bg,
+                             hipStream_t st) {
+  DibSmallIntArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.U = w + m.U; a.GU = w + m.g_u; a.batch = batch; a.K0 = l->F * l->E; a.params = params;
+  a.n_hidden = l->n_int;
+  for (int i = 0; i < l->n_int; ++i) { a.width[i] = l->int_units[i]; a.h[i] = w + m.int_h[i]; a.g[i] = w + m.g_int_h[i]; }
+  for (int i = 0; i <= l->n_int; ++i) { a.w_off[i] = l->int_w_off[i]; a.b_off[i] = l->int_b_off[i]; }
+  a.width[l->n_int] = l->out_dim;
+  a.act = l->act; a.out_act = l->out_act; a.out_dim = l->out_dim; a.mode = mode;
+  a.pred = w + m.pred; a.g_pred = w + m.g_pred;
+  a.loss_kind = loss_kind; a.Y = y; a.ldy = ldy; a.row_idx = (const int*)row_idx; a.row0 = row0; a.inv_bg = inv_bg;
+  a.partial_w = w + m.skinny_partial; a.partial_l = w + m.loss_partial;
+  // cluster mode: few row tiles, each on `cl` workgroups (dib_small.h)
+  const size_t cl_extra = (size_t)(DIB_SMALL_XCH_FLOATS_WIDE - DIB_SMALL_XCH_FLOATS) * sizeof(float);
+  int cl = small_cluster_size(a, (size_t)l->sb_int_lds + cl_extra);
+  if (t_companion.armed) {
+    t_companion.armed = false;
+    DibSmallIntPair p;
+    p.s[0] = a; p.s[1] = t_companion.args;
+    // the companion clusters by the same rule on its own size (training launches only: it has no exchange buffers for a launch
+    // without stashes); its arrival counters are the second half of this workspace's
+    DibSmallIntArgs& c = p.s[1];
+    int ccl = (c.mode & DIB_SMALL_INT_INFER) || small_tiles(c.batch) > small_tiles(batch) ? 1 : small_cluster_size(c, t_companion.lds + cl_extra);
+    // the two networks run side by side only while all their workgroups are resident (one per CU): the companion first gives up
+    // its cluster, then this network sizes itself next to it
+    if (small_tiles(batch) * cl + small_tiles(c.batch) * ccl > std::min(knobs().int_cluster_wgs, device_cus())) {
+      ccl = 1;
+      cl = small_cluster_size(a, (size_t)l->sb_int_lds + cl_extra, small_tiles(c.batch));
+    }
+    // the cluster grid carries BOTH networks' tiles and the wide exchange buffer: each network fitting on its own is not enough
+    // (a companion above 140 KB next to a clustered network) - then both run one workgroup per tile in the plain paired grid
+    if (std::max((size_t)l->sb_int_lds, t_companion.lds) + cl_extra > kSmallMaxLds) cl = ccl = 1;
+    if (cl > 1 || ccl > 1) {
+      p.s[0].cl = cl; p.s[0].cl_sync = (unsigned*)(w + m.cl_sync);
+      p.s[0].cl_agent_scope = c.cl_agent_scope = knobs().int_cluster_short_exchange ? 0 : 1;
+      for (int i = 0; i < l->n_int; ++i) p.s[0].xh[i] = w + m.cl_x[i];
+      c.cl = ccl; c.cl_sync = (unsigned*)(w + m.cl_sync) + (size_t)small_tiles(batch) * DIB_SMALL_CL_SYNC_WORDS;
+      const size_t lds = std::max((size_t)l->sb_int_lds, t_companion.lds) + cl_extra;
+      ProfScope ps(kProfOther, st);
+      const int gx = std::max(8 * cdiv(small_tiles(batch), 8) * cl, 8 * cdiv(small_tiles(c.batch), 8) * ccl);
+      return launch_lds<&dib_small_integration_pair_cluster_kernel>(dim3(gx, 2), dim3(DIB_SMALL_THREADS), lds, st, p);
+    }
+    const size_t lds = std::max((size_t)l->sb_int_lds, t_companion.lds);
+    ProfScope ps(kProfOther, st);
+    return launch_lds<&dib_small_integration_pair_kernel>(dim3(std::max(small_tiles(batch), small_tiles(p.s[1].batch)), 2),
+                                                          dim3(DIB_SMALL_THREADS), lds, st, p);
+  }
+  if (cl > 1) {
+    a.cl = cl; a.cl_sync = (unsigned*)(w + m.cl_sync); a.cl_agent_scope = knobs().int_cluster_short_exchange ? 0 : 1;
+    for (int i = 0; i < l->n_int; ++i) a.xh[i] = w + m.cl_x[i];
+    const size_t cl_lds = (size_t)l->sb_int_lds + cl_extra;
+    ProfScope ps(kProfOther, st);
+    return launch_lds<&dib_small_integration_cluster_kernel>(dim3(8 * cdiv(small_tiles(batch), 8) * cl), dim3(DIB_SMALL_THREADS), cl_lds,
+                                                             st, a);
+  }
+  ProfScope ps(kProfOther, st);
+  return launch_lds<&dib_small_integration_kernel>(dim3(small_tiles(batch)), dim3(DIB_SMALL_THREADS), (size_t)l->sb_int_lds, st, a);
+}
+
+// ---- plain MLP on the row-tile kernels (include/dib_hip.h dib_mlp_small_*): dib_small_integration_kernel with its input
+// tile built from the batch's rows of X (DIB_SMALL_INT_POSENC_IN) and the dgrad chain stopped at the first layer ----
+static int64_t mlp_small_lds_floats(const dib_mlp_desc* d) {
+  const int nf = d->n_freq > 1 ? d->n_freq : 1;
+  int64_t fl = (int64_t)DIB_SMALL_ROWS * dib_small_pitch(d->in_dim * nf);
+  for (int i = 0; i < d->n_hidden; ++i) fl += 2ll * DIB_SMALL_ROWS * dib_small_pitch(d->width[i]);
+  return fl + (int64_t)DIB_SMALL_ROWS * dib_small_pitch(d->width[d->n_hidden]) + DIB_SMALL_XCH_FLOATS;
+}
+static void mlp_small_fill(const dib_mlp_desc* d, DibSmallIntArgs& a, const float* params, int n) {
+  const int nf = d->n_freq > 1 ? d->n_freq : 1;
+  a.batch = n; a.K0 = d->in_dim * nf; a.params = params; a.n_hidden = d->n_hidden;
+  for (int i = 0; i <= d->n_hidden; ++i) { a.width[i] = d->width[i]; a.w_off[i] = d->w_off[i]; a.b_off[i] = d->b_off[i]; }
+  a.act = d->act; a.out_act = 0; a.out_dim = d->width[d->n_hidden];
+  a.in_dim = d->in_dim; a.n_freq = nf;
+}
+static int mlp_small_launch(const dib_mlp_desc* d, const DibSmallIntArgs& a, hipStream_t st) {
+  const size_t lds = (size_t)mlp_small_lds_floats(d) * 4;
+  ProfScope ps(kProfOther, st);
+  return launch_lds<&dib_small_integration_kernel>(dim3(small_tiles(a.batch)), dim3(DIB_SMALL_THREADS), lds, st, a);
+}
+// argument sets of the two passes (validated); DIB_OK, or the error the stand-alone entry point reports
+static int mlp_small_fwd_args(const dib_mlp_desc* d, const float* params, const float* x, int64_t ldx, const int32_t* row_idx, int n,
+                              float* a0, float* const* h, float* out, DibSmallIntArgs& a) {
+  if (!d || !params || !x || !out || n <= 0) return DIB_E_ARG;
+  if (!dib_mlp_small_supported(d, n)) return DIB_E_UNSUPPORTED;
+  bool stash = a0 != nullptr;
+  for (int i = 0; i < d->n_hidden; ++i) stash = stash && h != nullptr && h[i] != nullptr;
+  if (a0 != nullptr && !stash) return DIB_E_ARG;
+  std::memset(&a, 0, sizeof(a));
+  a.mode = DIB_SMALL_INT_FWD | DIB_SMALL_INT_OUT | DIB_SMALL_INT_POSENC_IN | (stash ? 0 : DIB_SMALL_INT_INFER);
+  a.X = x; a.ldx = ldx; a.row_idx = (const int*)row_idx; a.row0 = 0; a.a0 = a0; a.pred = out;
+  if (stash) for (int i = 0; i < d->n_hidden; ++i) a.h[i] = h[i];
+  mlp_small_fill(d, a, params, n);
+  return DIB_OK;
+}
+static int mlp_small_bwd_args(const dib_mlp_desc* d, const float* params, const float* g_out, float* const* h, float* const* g, int n,
+                              DibSmallIntArgs& a) {
+  if (!d || !params || !g_out || !h || !g || n <= 0) return DIB_E_ARG;
+  if (!dib_mlp_small_supported(d, n)) return DIB_E_UNSUPPORTED;
+  std::memset(&a, 0, sizeof(a));
+  a.mode = DIB_SMALL_INT_LOAD_H | DIB_SMALL_INT_BWD_OUT | DIB_SMALL_INT_BWD | DIB_SMALL_INT_NO_GU;
+  a.g_pred = const_cast<float*>(g_out);
+  for (int i = 0; i < d->n_hidden; ++i) {
+    if (!h[i] || !g[i]) return DIB_E_ARG;
+    a.h[i] = h[i]; a.g[i] = g[i];
+  }
+  mlp_small_fill(d, a, params, n);
+  return DIB_OK;
+}
+// ---- plain MLP with a 1-unit head: the whole training step of the head network in ONE launch (include/dib_hip.h) ----
+static int64_t mlp_head_lds_floats(const dib_mlp_desc* d) {
+  int64_t fl = (int64_t)DIB_SMALL_ROWS * dib_small_pitch(d->in_dim);
+  for (int i = 0; i < d->n_hidden; ++i) fl += 2ll * DIB_SMALL_ROWS * dib_small_pitch(d->width[i]);
+  return fl + (int64_t)DIB_SMALL_ROWS * dib_small_pitch(1) + DIB_SMALL_XCH_FLOATS + 9 * (d->width[d->n_hidden - 1] + 1) + 32;
+}
+
+// the companion protocol: arm, run the model's entry point, launch alone if the model's path had no row-tile launch to share
+static int with_companion(const dib_mlp_desc* d, const DibSmallIntArgs& c, hipStream_t st, int model_rc_fn(void*), void* ctx) {
+  t_companion.args = c;
+  t_companion.lds = (size_t)mlp_small_lds_floats(d) * 4;
+  t_companion.armed = true;
+  int rc = model_rc_fn(ctx);
+  if (t_companion.armed) {
+    t_companion.armed = false;
+    if (!rc) rc = mlp_small_launch(d, c, st);
+  }
+  return rc;
+}
+
+extern "C" {
+
+int dib_mlp_small_supported(const dib_mlp_desc* d, int batch) {
+  if (!d || !knobs().small_batch || !knobs().mlp_row_tiles || batch < 1 || batch > kSmallMaxBatch) return 0;
+  if (d->n_hidden < 1 || d->n_hidden > 3 || d->in_dim < 1) return 0;
+  if (!(d->act >= 0 && d->act <= 2) && d->act != DIB_ACT_LEAKY_RELU_01) return 0;   // piecewise-linear activations only
+  const int nf = d->n_freq > 1 ? d->n_freq : 1;
+  if ((int64_t)d->in_dim * nf > 1024) return 0;
+  for (int i = 0; i <= d->n_hidden; ++i)
+    if (d->width[i] < 16 || d->width[i] % 16 != 0 || d->width[i] > 1024) return 0;
+  return mlp_small_lds_floats(d) * 4 <= 150 * 1024 ? 1 : 0;
+}
+int dib_mlp_small_fwd(const dib_mlp_desc* d, const float* params, const float* x, int64_t ldx, const int32_t* row_idx, int n,
+                      float* a0, float* const* h, float* out, dib_stream_t stream) {
+  if (n == 0) return DIB_OK;
+  DibSmallIntArgs a;
+  if (int rc = mlp_small_fwd_args(d, params, x, ldx, row_idx, n, a0, h, out, a)) return rc;
+  return mlp_small_launch(d, a, (hipStream_t)stream);
+}
+int dib_mlp_small_bwd(const dib_mlp_desc* d, const float* params, const float* g_out, float* const* h, float* const* g, int n,
+                      dib_stream_t stream) {
+  if (n == 0) return DIB_OK;
+  DibSmallIntArgs a;
+  if (int rc = mlp_small_bwd_args(d, params, g_out, h, g, n, a)) return rc;
+  return mlp_small_launch(d, a, (hipStream_t)stream);
+}
+int dib_mlp_small_head_supported(const dib_mlp_desc* d, int n) {
+  if (!d || !knobs().small_batch || !knobs().mlp_row_tiles || n < 1 || n > kSmallMaxBatch) return 0;
+  if (d->n_hidden < 1 || d->n_hidden > 3 || d->in_dim < 16 || d->in_dim % 16 || d->in_dim > 1024 || d->n_freq > 1) return 0;
+  if (!(d->act >= 0 && d->act <= 2) && d->act != DIB_ACT_LEAKY_RELU_01) return 0;
+  for (int i = 0; i < d->n_hidden; ++i)
+    if (d->width[i] < 16 || d->width[i] % 16 != 0 || d->width[i] > 1024) return 0;
+  if (d->width[d->n_hidden] != 1) return 0;
+  return mlp_head_lds_floats(d) * 4 <= 150 * 1024 ? 1 : 0;
+}
+int64_t dib_mlp_small_head_workspace_bytes(const dib_mlp_desc* d, int n) {
+  if (!d || n < 1 || d->n_hidden < 1 || d->n_hidden > 3) return DIB_E_ARG;
+  return ((int64_t)small_tiles(n) * (d->width[d->n_hidden - 1] + 1 + 2) + 16) * (int64_t)sizeof(float);
+}
+int dib_mlp_small_head_step(const dib_mlp_desc* d, const float* params, const float* x, int n, const float* y, int64_t ldy,
+                            int loss_kind, float inv_global_batch, float* const* h, float* const* g, float* pred, float* g_pred,
+                            float* g_x, float* grads, float* sums3, void* ws, dib_stream_t stream) {
+  if (!d || !params || !x || !y || !h || !g || !pred || !g_pred || !grads || !sums3 || !ws || n <= 0) return DIB_E_ARG;
+  if (loss_kind != DIB_LOSS_BCE_LOGITS && loss_kind != DIB_LOSS_MSE) return DIB_E_UNSUPPORTED;
+  if (!dib_mlp_small_head_supported(d, n)) return DIB_E_UNSUPPORTED;
+  DibSmallIntArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.mode = DIB_SMALL_INT_FWD | DIB_SMALL_INT_HEAD | DIB_SMALL_INT_HEAD_GRAD | DIB_SMALL_INT_BWD | DIB_SMALL_INT_HEAD_REDUCE |
+           (g_x ? 0 : DIB_SMALL_INT_NO_GU);
+  a.U = x; a.GU = g_x; a.batch = n; a.K0 = d->in_dim; a.params = params; a.n_hidden = d->n_hidden;
+  for (int i = 0; i <= d->n_hidden; ++i) { a.width[i] = d->width[i]; a.w_off[i] = d->w_off[i]; a.b_off[i] = d->b_off[i]; }
+  for (int i = 0; i < d->n_hidden; ++i) {
+    if (!h[i] || !g[i]) return DIB_E_ARG;
+    a.h[i] = h[i]; a.g[i] = g[i];
+  }
+  a.act = d->act; a.out_act = 0; a.out_dim = 1;
+  a.pred = pred; a.g_pred = g_pred; a.loss_kind = loss_kind; a.Y = y; a.ldy = ldy; a.row_idx = nullptr; a.row0 = 0;
+  a.inv_bg = inv_global_batch;
+  const int tiles = small_tiles(n), KL = d->width[d->n_hidden - 1];
+  float* w = (float*)ws;
+  a.partial_w = w; a.partial_l = w + (int64_t)tiles * (KL + 1);
+  a.sync = (unsigned*)(a.partial_l + 2 * tiles);   // zero at first use (the caller zero-fills the workspace once)
+  a.head_gw = grads + d->w_off[d->n_hidden]; a.head_gb = grads + d->b_off[d->n_hidden];
+  a.sums3 = sums3; a.loss_scale = inv_global_batch;
+  const size_t lds = (size_t)mlp_head_lds_floats(d) * 4;
+  ProfScope ps(kProfOther, (hipStream_t)stream);
+  return launch_lds<&dib_small_integration_kernel>(dim3(tiles), dim3(DIB_SMALL_THREADS), lds, (hipStream_t)stream, a);
+}
+
+int dib_integration_fwd_and_mlp_fwd(dib_layout* l, int batch, const float* params, void* ws, const dib_mlp_desc* d,
+                                    const float* mlp_params, const float* x, int64_t ldx, const int32_t* row_idx, int n, float* a0,
+                                    float* const* h, float* out, dib_stream_t stream) {
+  DibSmallIntArgs c;
+  if (int rc = mlp_small_fwd_args(d, mlp_params, x, ldx, row_idx, n, a0, h, out, c)) return rc;
+  struct Ctx { dib_layout* l; int batch; const float* params; void* ws; dib_stream_t stream; } ctx{l, batch, params, ws, stream};
+  return with_companion(d, c, (hipStream_t)stream, [](void* p) {
+    Ctx* q = (Ctx*)p;
+    return dib_integration_fwd(q->l, q->batch, q->params, q->ws, q->stream);
+  }, &ctx);
+}
+int dib_backward_and_mlp_bwd(dib_layout* l, int batch, const float* params, float* grads, const float* beta_dev,
+                             float inv_global_batch, int flags, void* ws, const dib_mlp_desc* d, const float* mlp_params,
+                             const float* g_out, float* const* h, float* const* g, int n, dib_stream_t stream) {
+  DibSmallIntArgs c;
+  if (int rc = mlp_small_bwd_args(d, mlp_params, g_out, h, g, n, c)) return rc;
+  struct Ctx { dib_layout* l; int batch; const float* params; float* grads; const float* beta_dev; float inv; int flags; void* ws;
+               dib_stream_t stream; } ctx{l, batch, params, grads, beta_dev, inv_global_batch, flags, ws, stream};
+  return with_companion(d, c, (hipStream_t)stream, [](void* p) {
+    Ctx* q = (Ctx*)p;
+    return dib_backward(q->l, q->batch, q->params, q->grads, q->beta_dev, q->inv, q->flags, q->ws, q->stream);
+  }, &ctx);
+}
+
+#ifdef DIB_SMALL_TIMING
+// diagnostic build only (not declared in include/): phase marks of the last launches of the row-tile kernels (dib_small.h)
+int dib_small_debug_read(long long* out64) {
+  if (hipDeviceSynchronize() != hipSuccess) return DIB_E_ARG;
+  return (int)hipMemcpyFromSymbol(out64, HIP_SYMBOL(dib_small_dbg), 64 * sizeof(long long));
+}
+#endif
+
+}  // extern "C"

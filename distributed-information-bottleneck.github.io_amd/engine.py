@@ -598,7 +598,7 @@ def profile_summary(lib) -> dict:
     ms = (ctypes.c_double * PROFILE_CATEGORIES)()
     cnt = (c_int * PROFILE_CATEGORIES)()
     check(lib.dib_profile_summary(ms, cnt), "dib_profile_summary")
-    bk = lambda mode, ni, nj: 64 if (ni, nj) == (2, 2) or (mode, ni, nj) == (2, 1, 2) else 32  # csrc/dib_api.hip launch_gemm_t
+    bk = lambda mode, ni, nj: 64 if (ni, nj) == (2, 2) or (mode, ni, nj) == (2, 1, 2) else 32  # csrc/host/gemm.h launch_gemm_t
     names = [f"dib_gemm_kernel<{mode}, {ni}, {nj}, {bk(mode, ni, nj)}>"
              for mode in (0, 1, 2) for ni in (1, 2) for nj in (1, 2)]
     names += ["dib_fused_encoder_fwd_kernel", "dib_fused_encoder_bwd_kernel", "other", "dib_attn_fwd_kernel", "dib_attn_bwd_kernel"]

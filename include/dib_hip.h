@@ -30,8 +30,9 @@
  *     may use ONE layout with distinct workspaces (dib_workspace_init takes the layout's internal lock for its per-batch
  *     descriptor cache).  dib_layout_create / _upload_tables / _set_step_counter / _destroy of one layout are not
  *     concurrent with anything else that uses it.
- *   - The library keeps no other per-call state in globals: the first-launch kernel attributes (dynamic LDS limits, per device
- *     ordinal) are set under a lock and published before the launch that needs them; the compute-unit count of the split rule
+ *   - The library keeps no other per-call state in globals: a kernel's dynamic LDS limit (one high-water mark per kernel and
+ *     device ordinal, csrc/host/common.h launch_lds) is raised under a lock and published, once the runtime has accepted it,
+ *     before the launch that needs it - the steady state is one atomic load; the compute-unit count of the split rule
  *     is read from the calling thread's current device; dib_launch_count is a relaxed atomic sum over all threads.
  *   - dib_set_tuning is CONFIGURATION, not a per-call argument: it writes process-wide integers that every other entry
  *     point only reads.  Call it while no other entry point is running (start-up, or between steps of a single-threaded A/B);

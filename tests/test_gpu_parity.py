@@ -992,7 +992,7 @@ def test_north_star_architecture_multi_step_trajectory():
 
 
 def _random_spec(rng, row_tiles=False):
-    if row_tiles:   # architectures the row-tile kernels cover (csrc/dib_api.hip sb_enc / sb_int): widths % 16 == 0, inputs <= 15 wide
+    if row_tiles:   # architectures the row-tile kernels cover (csrc/host/layout.h sb_enc / sb_int): widths % 16 == 0, inputs <= 15 wide
         F = int(rng.integers(1, 6))
         pe = bool(rng.integers(0, 2))
         nf = int(rng.integers(1, 6)) if pe else 1
@@ -1423,7 +1423,7 @@ def test_alternating_entry_points_leave_no_stale_gradient_slabs(B):
     """A workspace holds `nsplit` partial slabs per parameter block and the reducers sum all of them; a weight-gradient launch that
     picks FEWER splits than an earlier launch over the same block (the split rule prices whole launches: at B = 512 the row-tile
     regime's one grouped launch picks 3 slabs, the per-layer launches behind dib_backward's custom-loss entry of a 1-unit output
-    pick 4) must not leave that launch's upper slabs in the sum (csrc/dib_api.hip retire_stale_slabs; found in round 6: a training step
+    pick 4) must not leave that launch's upper slabs in the sum (csrc/host/gemm.h retire_stale_slabs; found in round 6: a training step
     after a custom-loss step differed by 6e-3 in every GEMM-made gradient block).  Training step / custom-loss step / training
     step / custom-loss step on one engine = the bits of each on a fresh engine."""
     from dib_amd.engine import HipEngine

@@ -10,7 +10,7 @@ step of the categories the library's live profile counts (dib_profile_summary): 
 encoder-bank kernels.  The row-tile kernels themselves are "other" (not counted), so a step entirely on row tiles shows exactly
 one launch: the merged weight-gradient GEMM (mode 2) of dib_backward.  A silent fall-back shows up as extra GEMM launches.
 
-The counts come from the dispatch code (csrc/dib_api.hip, n = integration hidden layers):
+The counts come from the dispatch code (csrc/host/step.h and csrc/host/encoder.h, n = integration hidden layers):
   ROW     encoders + integration on row tiles, 1-unit head or out_dim % 16 == 0: merged wgrad only       train {g2: 1}, eval {}
   SKINNY  ... out_dim <= 8, not the head: output layer on the skinny kernels, every integration layer's backward (and so its
           dgrad) on GEMMs (integration_bwd_impl: no row-tile dgrad chain without a row-tile output layer), encoder wgrads 2, 3
@@ -232,7 +232,7 @@ REQUIRED = ({"enc.l1." + c for c in ("nt4:T%16", "nt2:T%8", "nt1:T%4", "nt2:T%2"
             | {f"cl.bwdcols.G2:{t}" for t in (6, 8, 10)} | {"cl.bwdcols.G0:7", "cl.bwdcols.G0:9"})
 
 
-def _int_lds(K0, units, out):   # csrc/dib_api.hip sb_int_lds (bytes) of the single-workgroup integration kernel
+def _int_lds(K0, units, out):   # csrc/host/layout.h sb_int_lds (bytes) of the single-workgroup integration kernel
     pitch = lambda w: (w + 63) // 64 * 64 + 4   # noqa: E731 (dib_small_pitch)
     fl = 16 * pitch(K0) + sum(2 * 16 * pitch(w) for w in units) + 16 * pitch(out) + 4 * 5 * 64 * 4 + 9 * (units[-1] + 1) + 32
     return 4 * fl
@@ -375,6 +375,57 @@ def test_row_tile_envelope_step_matches_oracle(name, tuning):
         assert _close(custom["pred"], cc.pred), "custom pred"
         assert _close(custom["g_u"], g_u_c, 3e-4), "custom g_u"
         _grads_close(eng, custom["grads"], grads_c)
+
+
+def _mlp_lds(K0, units, out):   # csrc/host/small.h mlp_small_lds_floats (bytes): dib_mlp_small_fwd launches the same kernel
+    pitch = lambda w: (w + 63) // 64 * 64 + 4   # noqa: E731 (dib_small_pitch)
+    return 4 * (16 * pitch(K0) + sum(2 * 16 * pitch(w) for w in units) + 16 * pitch(out) + 4 * 5 * 64 * 4)
+
+
+@pytest.mark.gpu
+def test_one_kernel_launched_with_two_lds_sizes_keeps_the_larger_limit(tuning):
+    """The dynamic-LDS limit above 64 KB is an attribute of the KERNEL FUNCTION (csrc/host/common.h launch_lds), and
+    dib_small_integration_kernel is launched from three places: the layout's integration network, dib_mlp_small_fwd / _bwd and
+    dib_mlp_small_head_step.  In one process: a layout step that needs 146 596 B, then a plain MLP that needs 95 744 B - more than
+    64 KB, less than the layout - then the layout step again.  A cache per call site would have the second call "raise" the limit to
+    its own, smaller size while the first site still believed in its own; with one high-water mark per kernel the limit only goes up.
+    Every call returns DIB_OK (check() raises otherwise: a refused launch is an error code) and the two layout steps give the same
+    bits."""
+    import ctypes
+    from dib_amd.dense import DenseStack
+    from dib_amd.engine import HipEngine
+    spec, B, mlp_units, mlp_out = _S([1, 1, 1, 1], [16, 16], [384, 384], 1, 32), 32, [256, 256], 16
+    int_lds = _int_lds(4 * 32, [384, 384], 1)
+    mlp_lds = _mlp_lds(2, mlp_units, mlp_out)
+    assert 64 * 1024 < mlp_lds < int_lds <= 150 * 1024, (mlp_lds, int_lds)
+    tuning({"int_cluster": 0})   # the plain dib_small_integration_kernel, not its cluster variant (a kernel of its own)
+    eng = HipEngine(**spec_kwargs(spec), init_seed=5)
+    eng.set_flat_params(params_to_flat(eng.blocks, random_params(spec, 5), eng.params.numel()))
+    eng.set_beta(0.29)
+    rng = np.random.default_rng(5)
+    xd = eng.to_device(rng.standard_normal((B, 4)).astype(np.float32))
+    yd = eng.to_device(rng.integers(0, 2, (B, 1)).astype(np.float32))
+
+    def layout_step():
+        eng.profile_enable(True)
+        try:
+            eng.train_step(xd, yd, None, 0, B, 11, 4, "bce_logits")
+            torch.cuda.synchronize()
+            assert _counts(eng) == ROW[0]   # integration network and head on the row-tile kernel: the merged wgrad is the only GEMM
+        finally:
+            eng.profile_enable(False)
+        return dict(pred=eng.pred(B).clone(), so=eng.step_out(B).clone(), g_u=eng.g_u(B).clone(), grads=eng.grads.clone())
+
+    first = layout_step()
+    stack = DenseStack(eng, 2, mlp_units, mlp_out, activation="relu", use_positional_encoding=False, seed=3)
+    assert eng.lib.dib_mlp_small_supported(ctypes.byref(stack._desc), B) == 1
+    out = stack.forward(eng.to_device(rng.standard_normal((B, 2)).astype(np.float32)))   # dib_mlp_small_fwd, checked
+    torch.cuda.synchronize()
+    assert stack._last["small"] and out.shape == (B, mlp_out) and torch.isfinite(out).all()
+    again = layout_step()
+    for k in first:
+        assert torch.equal(first[k], again[k]), k
+    assert torch.isfinite(first["grads"]).all()
 
 
 # ---- the paired grid (dib_integration_fwd_and_mlp_fwd / dib_backward_and_mlp_bwd) against the oracle ------------------------

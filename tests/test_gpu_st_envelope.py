@@ -53,14 +53,14 @@ D_ATT = 128
 
 
 def attn_fwd_path(P, fwd_waves=8):
-    """csrc/dib_api.hip dib_attention_fwd"""
+    """csrc/host/st.h dib_attention_fwd"""
     if P <= 64:
         return "small"
     return "flash8" if fwd_waves == 8 and P >= 256 else "flash4"
 
 
 def attn_bwd_path(P, small_waves=8):
-    """csrc/dib_api.hip dib_attention_bwd: the single-workgroup kernel (8 or 4 waves) or the flash kernel (+ dQ reduce)"""
+    """csrc/host/st.h dib_attention_bwd: the single-workgroup kernel (8 or 4 waves) or the flash kernel (+ dQ reduce)"""
     if P <= 64:
         return "small8" if small_waves >= 8 else "small4"
     return "flash_dq_reduce" if (P + 127) // 128 > 1 else "flash_one_key_block"
@@ -107,7 +107,7 @@ def st_chain_bwd_lds(D, HK, ff):
 
 
 def st_chain_supported(D, HK, ff, act, T, small_batch=1):
-    """csrc/dib_api.hip dib_st_chain_supported"""
+    """csrc/host/st.h dib_st_chain_supported"""
     if T <= 0 or not small_batch:
         return False
     if D <= 0 or D % 32 or D > 256 or HK <= 0 or HK % 16 or not 1 <= len(ff) <= 3:
