@@ -13,8 +13,9 @@ from . import circuit  # noqa: F401
 from .circuit import CircuitIB  # noqa: F401
 from . import random_partition  # noqa: F401
 from .random_partition import RandomPartition  # noqa: F401
+from . import mi_characterization  # noqa: F401
 
 __all__ = ["DistributedIBNet", "InfoBottleneckAnnealingCallback", "SaveCompressionMatricesCallback",
            "InfoPerFeatureCallback", "PositionalEncoding", "Callback", "History", "models", "losses", "optimizers", "data", "utils",
            "visualization", "ctw", "chaos_data", "set_transformer", "SetTransformerDIB", "measurement", "MeasurementIB",
-           "circuit", "CircuitIB", "random_partition", "RandomPartition"]
+           "circuit", "CircuitIB", "random_partition", "RandomPartition", "mi_characterization"]

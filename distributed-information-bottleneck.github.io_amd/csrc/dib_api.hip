@@ -27,10 +27,12 @@
 #include "dib_circuit.h"
 #include "dib_partition.h"
 #include "dib_st_info.h"
+#include "dib_mi_channel.h"
 #include "../../include/dib_st.h"
 #include "../../include/dib_measure.h"
 #include "../../include/dib_circuit.h"
 #include "../../include/dib_partition.h"
+#include "../../include/dib_mi_channel.h"
 
 // The host code, by family, in dependency order (this file is the only translation unit).
 #include "host/common.h"
@@ -44,3 +46,4 @@
 #include "host/measure.h"
 #include "host/circuit.h"
 #include "host/partition.h"
+#include "host/mi_channel.h"

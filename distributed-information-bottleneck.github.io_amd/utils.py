@@ -121,3 +121,64 @@ def _circuit_mi_bounds(encoder, x, n, bs, rng, number_evaluation_batches, seed):
                                          ctypes.c_void_p(torch.cuda.current_stream(m.device).cuda_stream)), "dib_mi_sandwich_rows")
         estimates.append(r.mean(dim=1).cpu().numpy())
     return np.mean(np.stack(estimates, 0), 0)
+
+
+# Most batch rows (batches x evaluation_batch_size) of one dib_mi_sandwich_batched launch: 2^24 (its index upload is 64 MiB and
+# its workspace 24 bytes per row); more batches than that - or than the kernel's 65 535 groups - are evaluated in several launches
+_SANDWICH_ROWS_PER_LAUNCH = 1 << 24
+
+
+def _sandwich_bounds_of_rows(table, rows, seed, step0=0):
+    """dib_mi_sandwich_batched with one row per "neighbourhood" (P = 1, logvar offset 0) on a parameter table [N, 2E] (mu | logvar):
+    batch b = the table rows rows[b] (repeats allowed), its noise keyed (seed, step0 + b, position in the batch, 0).
+    Returns [batches, 2] (lower, upper) per batch in nats."""
+    import ctypes
+
+    import torch
+
+    from ._lib import check, load_library
+    table = np.ascontiguousarray(table, dtype=np.float32)
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    n, e = table.shape[0], table.shape[1] // 2
+    nb, bs = rows.shape
+    if rows.size == 0 or rows.min() < 0 or rows.max() >= n:
+        raise ValueError("batch rows must index the parameter table")
+    if not torch.cuda.is_available():
+        raise RuntimeError("the sandwich bounds are evaluated on the GPU (there is no CPU fallback)")
+    lib = load_library()
+    per_launch = max(1, min(65535, _SANDWICH_ROWS_PER_LAUNCH // bs, nb))
+    # (the last launch may hold fewer batches, and fewer batches can mean more row splits: size the workspace for both)
+    needs = [int(lib.dib_mi_sandwich_batched_workspace_bytes(n, 1, e, g, bs)) for g in {per_launch, nb % per_launch or per_launch}]
+    need = min(needs) if min(needs) < 0 else max(needs)
+    if need < 0:
+        raise ValueError(f"dib_mi_sandwich_batched: outside the envelope (E {e} must be a multiple of 4 up to 256, batch size {bs} >= 2)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    tab_d = torch.from_numpy(table).to(dev)
+    ws = torch.empty(need // 8 + 2, dtype=torch.float64, device=dev)
+    out = torch.empty((2, nb), dtype=torch.float64, device=dev)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    null = ctypes.c_void_p(0)
+    for b0 in range(0, nb, per_launch):
+        b1 = min(nb, b0 + per_launch)
+        idx_d = torch.from_numpy(rows[b0:b1]).to(dev)
+        check(lib.dib_mi_sandwich_batched(ctypes.c_void_p(tab_d.data_ptr()), n, 1, e, ctypes.c_void_p(idx_d.data_ptr()), b1 - b0, bs,
+                                          0.0, int(seed) & (2 ** 64 - 1), (int(step0) + b0) & 0xFFFFFFFF,
+                                          ctypes.c_void_p(out[0, b0:].data_ptr()), ctypes.c_void_p(out[1, b0:].data_ptr()), null, null,
+                                          null, ctypes.c_void_p(ws.data_ptr()), stream), "dib_mi_sandwich_batched")
+    return out.cpu().numpy().T.copy()
+
+
+def estimate_mi_sandwich_bounds_from_parameters(mus, logvars, evaluation_batch_size=1024, number_evaluation_batches=8, seed=0):
+    """The sandwich bounds of a channel given by its parameters, with no encoder and no dataset (the MI-bound characterization
+    notebook's estimate_mi_sandwich_bounds(mus, logvars, ...)): p(u|x_j) = N(mus[j], diag exp(logvars[j])), [N, E] each.
+
+    Returns [number_evaluation_batches, 2]: per batch the (InfoNCE lower, leave-one-out upper) bound in BITS, as the notebook's
+    function does.  Batch b is rows np.random.default_rng(seed).integers(0, N, (number_evaluation_batches,
+    evaluation_batch_size))[b] of the table - drawn with replacement, where the notebook calls np.random.choice - with the noise
+    of dib_mi_sandwich_rows keyed (seed, step b, position, feature 0).  All batches go through ONE dib_mi_sandwich_batched launch
+    (P = 1), in float64 with a log-sum-exp; the call is split only beyond 2^24 batch rows or 65 535 batches."""
+    mus, logvars = np.asarray(mus, dtype=np.float32), np.asarray(logvars, dtype=np.float32)
+    if mus.ndim != 2 or mus.shape != logvars.shape:
+        raise ValueError(f"mus {mus.shape} and logvars {logvars.shape} must both be [N, E]")
+    rows = np.random.default_rng(seed).integers(0, mus.shape[0], (int(number_evaluation_batches), int(evaluation_batch_size)))
+    return _sandwich_bounds_of_rows(np.concatenate([mus, logvars], -1), rows, seed) / np.log(2.0)

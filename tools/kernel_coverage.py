@@ -66,6 +66,9 @@ ORACLE_TESTS = {
     "test_gpu_st_information.py": {
         "test_batched_sandwich_bounds_match_oracle", "test_probe_map_matches_oracle", "test_far_apart_gaussians_stay_finite",
         "test_notebook_batch_size_on_a_subset_of_probes", "test_information_bounds_match_the_oracle_on_the_model_encodings"},
+    "test_gpu_mi_characterization.py": {
+        "test_kernel_matches_oracle_across_the_envelope", "test_far_apart_gaussians_stay_finite",
+        "test_bounds_from_parameters_equal_the_rows_loop_and_the_oracle", "test_known_answer_on_the_device"},
 }
 # tests that demand the bits (or fp32 summation-order tolerance) of a path the tests above check against an oracle
 EQUIVALENCE_TESTS = {
@@ -87,6 +90,9 @@ EQUIVALENCE_TESTS = {
         "test_batched_sandwich_equals_the_per_batch_rows_loop", "test_probe_map_equals_the_probe_bounds_loop",
         "test_information_maps_equal_information_map", "test_replay_is_bit_identical_and_bad_arguments_are_refused",
         "test_tracked_fit_trains_exactly_like_the_untracked_fit"},
+    "test_gpu_mi_characterization.py": {
+        "test_replay_split_calls_and_refusals", "test_bounds_from_parameters_reproduce_the_separation_zero_anchors",
+        "test_characterize_on_a_small_sweep"},
 }
 
 
