@@ -14,6 +14,8 @@
 
 #include "../../include/dib_hip.h"
 #include "dib_elementwise.h"
+#include "dib_gauss_lse.h"
+#include "dib_mi_rows.h"
 #include "dib_gemm.h"
 #include "dib_infonce_mfma.h"
 #include "dib_fused.h"
@@ -43,7 +45,7 @@
 #include "host/step.h"
 #include "host/infonce.h"
 #include "host/st.h"
+#include "host/mi.h"
 #include "host/measure.h"
 #include "host/circuit.h"
 #include "host/partition.h"
-#include "host/mi_channel.h"

@@ -14,6 +14,7 @@
 // eps draws, which keep the library's key (seed, step, row b, feature g, dim 0).
 #pragma once
 #include "dib_common.h"
+#include "dib_gauss_lse.h"
 
 #define DIB_CIRCUIT_MAX_GATES 16
 #define DIB_CIRCUIT_MAX_BATCH 2048
@@ -107,12 +108,6 @@ dib_circuit_bwd_kernel(const uint32_t* __restrict__ table, int G, int B, const f
 // order: out[g][b] = {lower, upper} (nats), the same bits every call.
 #define DIB_CIRCUIT_MI_ROWS 64
 
-__device__ __forceinline__ void dib_circuit_lse_merge(double& mx, double& sm, double m2, double s2) {
-  const double m = mx > m2 ? mx : m2;
-  sm = sm * exp(mx - m) + s2 * exp(m2 - m);
-  mx = m;
-}
-
 __global__ void __launch_bounds__(256)
 dib_circuit_mi_kernel(const float* __restrict__ sc, int G, const float* __restrict__ xs, int n, int nb, uint64_t seed,
                       double* __restrict__ part_ws, unsigned* __restrict__ counters, double* __restrict__ out) {
@@ -127,7 +122,7 @@ dib_circuit_mi_kernel(const float* __restrict__ sc, int G, const float* __restri
   const double l = (double)sc[G + g];
   const double sd = exp(0.5 * l);
   const double is = 1.0 / sd;
-  const double c = -0.5 * l - 0.5 * 1.8378770664093454835606594728112;   // log N(0; 0, sigma^2), ln(2 pi) = 1.8378...
+  const double c = -0.5 * l - 0.5 * DIB_LN2PI;   // log N(0; 0, sigma^2)
   const float mu_i = valid ? x[i] * s : 0.f;
   const double ui = valid ? (double)mu_i + sd * (double)dib_circuit_eps(seed, (uint32_t)b, (uint32_t)i, (uint32_t)g) : 0.0;
   double mx = -1.0e300, sm = 0.0;   // log-sum-exp over j != i
@@ -135,27 +130,21 @@ dib_circuit_mi_kernel(const float* __restrict__ sc, int G, const float* __restri
     for (int j = q; j < n; j += 4) {
       if (j == i) continue;
       const double d = (ui - (double)(x[j] * s)) * is;
-      const double v = c - 0.5 * (d * d);
-      if (v > mx) { sm = sm * exp(mx - v) + 1.0; mx = v; }
-      else sm += exp(v - mx);
+      dib_lse_add(mx, sm, c - 0.5 * (d * d));
     }
   }
 #pragma unroll
   for (int o = 1; o <= 2; o <<= 1) {
     const double m2 = __shfl_xor(mx, o, 64), s2 = __shfl_xor(sm, o, 64);
-    dib_circuit_lse_merge(mx, sm, m2, s2);
+    dib_lse_merge(mx, sm, m2, s2);
   }
   if (q == 0) {
     double lo = 0.0, up = 0.0;
     if (valid) {
       const double d = (ui - (double)mu_i) * is;
       const double lii = c - 0.5 * (d * d);
-      const double lse_off = (sm > 0.0) ? mx + log(sm) : -INFINITY;
-      const double mall = lii > lse_off ? lii : lse_off;
-      const double lse_all = mall + log(exp(lii - mall) + exp(lse_off - mall));
       const double logn = log((double)n);
-      lo = lii - (lse_all - logn);
-      up = lii - (lse_off - logn);
+      dib_sandwich_pair(lii, dib_lse_value(mx, sm), logn, logn, lo, up);
     }
     rlo[r] = lo;
     rup[r] = up;

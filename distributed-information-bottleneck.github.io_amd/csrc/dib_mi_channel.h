@@ -2,8 +2,7 @@
 // reference's MI-bound characterization notebook, paper Fig. S4): term = l_r - (LSE_j l_j - log n_rows) per sample, the sample
 // drawn from row r of the group's table, l_j over every row of that table, float64 with a log-sum-exp.
 //
-// The arithmetic is dib_st_info.h's: dib_sti_table_kernel folds the stacked tables into (1/sigma, mu/sigma) per dimension and
-// c_j per row, a term costs two FMAs per (sample, row, dimension), partials are (max, sum) pairs.  What differs is where a
+// The arithmetic is dib_gauss_lse.h's, on tables folded by dib_sti_table_kernel (dib_st_info.h).  What differs is where a
 // sample's own conditional comes from: not an extra term beside the data rows but ONE of them, chosen by index - so l_r is
 // evaluated from the folded row r with the very FMA sequence of the row loop (the same bits as that row's l_j: for Gaussians far
 // apart l_r - LSE is exactly -log(multiplicity)), and no row is ever excluded.
@@ -13,11 +12,11 @@
 // rows per pass.  The staged rows are padded to blocks of 8 dimensions with (0, 0) and the samples with 0, so the dimension
 // loop branches once per block (16 LDS reads in flight) and a padded dimension adds exactly 0 to q.  Each workgroup leaves one
 // (max, sum) per sample; dib_mic_combine_kernel merges the splits in order, forms the terms and reduces a group's terms by a
-// fixed tree.  The split count is a function of (n_rows, n_samples) alone (host/mi_channel.h), never of the number of groups:
+// fixed tree.  The split count is a function of (n_rows, n_samples) alone (host/mi.h), never of the number of groups:
 // a group's bits do not depend on which other groups share its launch.
 #pragma once
 #include "dib_common.h"
-#include "dib_st_info.h"
+#include "dib_gauss_lse.h"
 
 #define DIB_MIC_THREADS 256
 
@@ -80,17 +79,9 @@ dib_mic_terms_kernel(DibMicArgs a) {
   }
   if (s == 0 && wave == 0 && act) {
     // own log-density from the folded row r: the FMA sequence of the row loop below
-    const double2* w = a.tab + (row0 + r) * E;
-    double q = 0.0;
-#pragma unroll
-    for (int e = 0; e < EMAX; ++e) {
-      if (e < E) {
-        const double2 w0 = w[e];
-        const double d = fma(u[e], w0.x, -w0.y);
-        q = fma(d, d, q);
-      }
-    }
-    a.lr[(long long)g * a.npad + si] = bad ? (double)NAN : a.tab_c[row0 + r] - 0.5 * q;
+    double q[1] = {0.0};
+    dib_gauss_q<EMAX, 1, 1>(a.tab + (row0 + r) * E, 0, E, u, nullptr, lane, q);
+    a.lr[(long long)g * a.npad + si] = bad ? (double)NAN : a.tab_c[row0 + r] - 0.5 * q[0];
   }
   double mx = -1.0e300, sm = 0.0;
   const int r0 = s * a.rps, r1 = min(a.n_rows, r0 + a.rps);
@@ -105,54 +96,11 @@ dib_mic_terms_kernel(DibMicArgs a) {
     for (int j = threadIdx.x; j < nrow; j += DIB_MIC_THREADS) st_c[j] = a.tab_c[row0 + base + j];
     __syncthreads();
     if (!act) continue;
-    int j = wave;
-    for (; j + 4 < nrow; j += 8) {   // two rows per pass: independent FMA chains
-      const double2* t0 = st + (long long)j * Ep;
-      const double2* t1 = t0 + 4 * Ep;
-      double q0 = 0.0, q1 = 0.0;
-#pragma unroll
-      for (int c = 0; c < EMAX / 8; ++c) {
-        if (8 * c < E) {
-#pragma unroll
-          for (int k = 0; k < 8; ++k) {
-            const int e = 8 * c + k;
-            const double2 w0 = t0[e], w1 = t1[e];
-            const double d0 = fma(u[e], w0.x, -w0.y), d1 = fma(u[e], w1.x, -w1.y);
-            q0 = fma(d0, d0, q0);
-            q1 = fma(d1, d1, q1);
-          }
-        }
-      }
-      dib_sti_lse_add(mx, sm, st_c[j] - 0.5 * q0);
-      dib_sti_lse_add(mx, sm, st_c[j + 4] - 0.5 * q1);
-    }
-    for (; j < nrow; j += 4) {
-      const double2* t0 = st + (long long)j * Ep;
-      double q0 = 0.0;
-#pragma unroll
-      for (int c = 0; c < EMAX / 8; ++c) {
-        if (8 * c < E) {
-#pragma unroll
-          for (int k = 0; k < 8; ++k) {
-            const int e = 8 * c + k;
-            const double2 w0 = t0[e];
-            const double d0 = fma(u[e], w0.x, -w0.y);
-            q0 = fma(d0, d0, q0);
-          }
-        }
-      }
-      dib_sti_lse_add(mx, sm, st_c[j] - 0.5 * q0);
-    }
+    dib_gauss_block_lse<EMAX, 8, false>(st, st_c, Ep, E, nrow, wave, lane, u, nullptr, 0, mx, sm);
   }
   // the four waves' partials of each sample, merged in wave order
-  __syncthreads();
-  red[wave * 64 + lane] = make_double2(mx, sm);
-  __syncthreads();
-  if (wave == 0 && act) {
-    double m = red[lane].x, sum = red[lane].y;
-    for (int w = 1; w < 4; ++w) dib_sti_lse_merge(m, sum, red[w * 64 + lane].x, red[w * 64 + lane].y);
-    a.part[((long long)s * a.G + g) * a.npad + si] = make_double2(m, sum);
-  }
+  dib_lse_merge_waves(red, wave, lane, mx, sm);
+  if (wave == 0 && act) a.part[((long long)s * a.G + g) * a.npad + si] = make_double2(mx, sm);
 }
 
 // one workgroup per group: the splits of each sample merged in split order, term = l_r - (LSE - log n_rows) (optionally written),
@@ -164,13 +112,9 @@ dib_mic_combine_kernel(DibMicArgs a, double* __restrict__ group_means, double* _
   const double logn = log((double)a.n_rows);
   double acc = 0.0;
   for (int i = threadIdx.x; i < a.n_samples; i += 256) {
-    double2 p = a.part[(long long)g * a.npad + i];
-    double m = p.x, sum = p.y;
-    for (int s = 1; s < a.S; ++s) {
-      p = a.part[((long long)s * a.G + g) * a.npad + i];
-      dib_sti_lse_merge(m, sum, p.x, p.y);
-    }
-    const double term = a.lr[(long long)g * a.npad + i] - (m + log(sum) - logn);
+    const double2 p = dib_lse_of_splits(a.part, a.S, (long long)a.G * a.npad, (long long)g * a.npad + i);
+    // (not dib_lse_value: every row is summed, so the sum is 0 only where its log is -inf anyway, and a NaN table stays NaN)
+    const double term = a.lr[(long long)g * a.npad + i] - (p.x + log(p.y) - logn);
     if (sample_terms) sample_terms[(long long)g * a.n_samples + i] = term;
     acc += term;
   }

@@ -2,11 +2,10 @@
 // dib_mi_sandwich_batched): the per-particle probe-grid map and the batched sandwich bounds on I(U;X), each as ONE tiled launch
 // (+ a table prep and a fixed-order combine) over an encoded table of validation particles.
 //
-// Both evaluate l_ij = log N(u_i; mu_j, diag(sigma_j^2)) in float64 with a log-sum-exp, like dib_mi_rows_kernel /
-// dib_mi_probe_rows_kernel.  The data Gaussians come from the table [n_rows][2E] (mu | raw logvar): a group's rows are the
-// neighbourhoods it names (neighbourhood k = rows k P .. k P + P - 1).  dib_sti_table_kernel folds 1 / sigma into the table once,
-// (1/sigma_e, mu_e/sigma_e) per dimension and c_j = -1/2 sum_e logvar_je - E/2 ln(2 pi) per row, so a term costs two FMAs:
-// d = u_e (1/sigma_e) - mu_e/sigma_e, q += d d.
+// Both evaluate l_ij = log N(u_i; mu_j, diag(sigma_j^2)) with the arithmetic of dib_gauss_lse.h (the row loop, the merges and the
+// closing formula live there).  The data Gaussians come from the table [n_rows][2E] (mu | raw logvar): a group's rows are the
+// neighbourhoods it names (neighbourhood k = rows k P .. k P + P - 1).  dib_sti_table_kernel folds 1 / sigma into the table once:
+// (1/sigma_e, mu_e/sigma_e) per dimension and c_j per row.
 //
 // dib_sti_bounds_kernel: grid (probe tiles of 64, groups, row splits), 256 threads.  Lane = probe, wave = every fourth row of a
 // block of `rb` data rows staged in LDS (every lane of a wave reads the same row: broadcasts).  A probe's sample u lives in
@@ -20,9 +19,9 @@
 //     drawn twice contributes its rows twice); per-batch means.
 #pragma once
 #include "dib_common.h"
+#include "dib_gauss_lse.h"
 
 #define DIB_STI_THREADS 256
-#define DIB_STI_LN2PI 1.8378770664093454835606594728112
 
 struct DibStiArgs {
   const float* enc_probe;      // map mode: [M][2E]; sandwich mode: unused (the probes are table rows)
@@ -40,17 +39,6 @@ struct DibStiArgs {
   int sandwich, E, P, n_nbhd, n_table_nbhd, M, C, nb, G, S, npad, rps, rb, gstride;
 };
 
-__device__ __forceinline__ void dib_sti_lse_add(double& mx, double& sm, double v) {
-  if (v > mx) { sm = sm * exp(mx - v) + 1.0; mx = v; }
-  else sm += exp(v - mx);
-}
-
-__device__ __forceinline__ void dib_sti_lse_merge(double& mx, double& sm, double m2, double s2) {
-  const double m = mx > m2 ? mx : m2;
-  sm = sm * exp(mx - m) + s2 * exp(m2 - m);
-  mx = m;
-}
-
 // (1/sigma, mu/sigma) per (row, dimension) and c per row; one thread per row, dimensions in order (c as dib_mi_prep_kernel)
 __global__ void __launch_bounds__(256)
 dib_sti_table_kernel(const float* __restrict__ enc, long long n_rows, int E, float lv_off, double2* __restrict__ tab,
@@ -66,7 +54,7 @@ dib_sti_table_kernel(const float* __restrict__ enc, long long n_rows, int E, flo
     tab[j * E + e] = make_double2(is, (double)mu[e] * is);
     slv += l;
   }
-  tab_c[j] = -0.5 * slv - 0.5 * (double)E * DIB_STI_LN2PI;
+  tab_c[j] = -0.5 * slv - 0.5 * (double)E * DIB_LN2PI;
 }
 
 // table row of data row j of group g (-1: an index outside the table)
@@ -113,30 +101,13 @@ dib_sti_bounds_kernel(DibStiArgs a) {
     double slv = 0.0, q = 0.0;
     const float* mu = enc;
     const float* lv = enc + E;
-    if (EMAX > 0) {
-#pragma unroll
-      for (int qd = 0; qd < (EMAX > 0 ? EMAX : 4) / 4; ++qd) {
-        if (4 * qd < E) {
-          float eps[4];
-          dib_eps4(a.seed, step, (uint32_t)pi, 0u, (uint32_t)qd, eps);
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            const int e = 4 * qd + t;
-            const double l = (double)lv[e] + (double)a.lv_off;
-            const double sd = exp(0.5 * l);
-            const double is = 1.0 / sd;
-            const double ue = (double)mu[e] + sd * (double)eps[t];
-            const double d = (ue - (double)mu[e]) * is;
-            q = fma(d, d, q);
-            slv += l;
-            u[(EMAX > 0 ? e : 0)] = ue;
-          }
-        }
-      }
-    } else {
-      for (int qd = 0; qd < E / 4; ++qd) {
+    constexpr int kQuads = EMAX / 4;   // registers: a compile-time trip count, fully unrolled; LDS: E / 4 quads, not unrolled
+#pragma unroll kQuads > 0 ? kQuads : 1
+    for (int qd = 0; qd < (EMAX > 0 ? kQuads : E / 4); ++qd) {
+      if (EMAX == 0 || 4 * qd < E) {
         float eps[4];
         dib_eps4(a.seed, step, (uint32_t)pi, 0u, (uint32_t)qd, eps);
+#pragma unroll
         for (int t = 0; t < 4; ++t) {
           const int e = 4 * qd + t;
           const double l = (double)lv[e] + (double)a.lv_off;
@@ -146,11 +117,12 @@ dib_sti_bounds_kernel(DibStiArgs a) {
           const double d = (ue - (double)mu[e]) * is;
           q = fma(d, d, q);
           slv += l;
-          if (wave == 0) u_lds[e * 64 + lane] = ue;
+          if (EMAX > 0) u[EMAX > 0 ? e : 0] = ue;
+          else if (wave == 0) u_lds[e * 64 + lane] = ue;
         }
       }
     }
-    const double c = -0.5 * slv - 0.5 * (double)E * DIB_STI_LN2PI;
+    const double c = -0.5 * slv - 0.5 * (double)E * DIB_LN2PI;
     lii = bad ? (double)NAN : c - 0.5 * q;
   }
   if (a.u_out && act && s == 0 && wave == 0) {
@@ -187,85 +159,20 @@ dib_sti_bounds_kernel(DibStiArgs a) {
     }
     __syncthreads();
     if (!act) continue;
-    int r = wave;
-    for (; r + 4 < nrow; r += 8) {   // two rows per pass: independent FMA chains
-      const double2* t0 = st + (long long)r * E;
-      const double2* t1 = t0 + 4 * E;
-      double q0 = 0.0, q1 = 0.0;
-      if (EMAX > 0) {
-#pragma unroll
-        for (int e = 0; e < (EMAX > 0 ? EMAX : 1); ++e) {
-          if (e < E) {
-            const double2 w0 = t0[e], w1 = t1[e];
-            const double d0 = fma(u[e], w0.x, -w0.y), d1 = fma(u[e], w1.x, -w1.y);
-            q0 = fma(d0, d0, q0);
-            q1 = fma(d1, d1, q1);
-          }
-        }
-      } else {
-        for (int e = 0; e < E; ++e) {
-          const double ue = u_lds[e * 64 + lane];
-          const double2 w0 = t0[e], w1 = t1[e];
-          const double d0 = fma(ue, w0.x, -w0.y), d1 = fma(ue, w1.x, -w1.y);
-          q0 = fma(d0, d0, q0);
-          q1 = fma(d1, d1, q1);
-        }
-      }
-      double v0 = st_c[r] - 0.5 * q0, v1 = st_c[r + 4] - 0.5 * q1;
-      if (a.sandwich && base + r == pi) v0 = -INFINITY;
-      if (a.sandwich && base + r + 4 == pi) v1 = -INFINITY;
-      dib_sti_lse_add(mx, sm, v0);
-      dib_sti_lse_add(mx, sm, v1);
-    }
-    for (; r < nrow; r += 4) {
-      const double2* t0 = st + (long long)r * E;
-      double q0 = 0.0;
-      if (EMAX > 0) {
-#pragma unroll
-        for (int e = 0; e < (EMAX > 0 ? EMAX : 1); ++e) {
-          if (e < E) {
-            const double2 w0 = t0[e];
-            const double d0 = fma(u[e], w0.x, -w0.y);
-            q0 = fma(d0, d0, q0);
-          }
-        }
-      } else {
-        for (int e = 0; e < E; ++e) {
-          const double2 w0 = t0[e];
-          const double d0 = fma(u_lds[e * 64 + lane], w0.x, -w0.y);
-          q0 = fma(d0, d0, q0);
-        }
-      }
-      double v0 = st_c[r] - 0.5 * q0;
-      if (a.sandwich && base + r == pi) v0 = -INFINITY;
-      dib_sti_lse_add(mx, sm, v0);
-    }
+    dib_gauss_block_lse<EMAX, 1, true>(st, st_c, E, E, nrow, wave, lane, u, u_lds, a.sandwich ? pi - base : -1, mx, sm);
   }
   // the four waves' partials of each probe, merged in wave order
-  __syncthreads();
-  red[wave * 64 + lane] = make_double2(mx, sm);
-  __syncthreads();
+  dib_lse_merge_waves(red, wave, lane, mx, sm);
   if (wave == 0 && act) {
-    double m = red[lane].x, sum = red[lane].y;
-    for (int w = 1; w < 4; ++w) dib_sti_lse_merge(m, sum, red[w * 64 + lane].x, red[w * 64 + lane].y);
-    a.part[((long long)s * a.G + g) * a.npad + pi] = make_double2(m, sum);
+    a.part[((long long)s * a.G + g) * a.npad + pi] = make_double2(mx, sm);
     if (s == 0) a.lii[(long long)g * a.npad + pi] = lii;
   }
 }
 
-__device__ __forceinline__ double dib_sti_lse_of(const DibStiArgs& a, int g, int i) {
-  double2 p = a.part[(long long)g * a.npad + i];
-  double m = p.x, sum = p.y;
-  for (int s = 1; s < a.S; ++s) {
-    p = a.part[((long long)s * a.G + g) * a.npad + i];
-    dib_sti_lse_merge(m, sum, p.x, p.y);
-  }
-  return sum > 0.0 ? m + log(sum) : -INFINITY;
-}
-
-__device__ __forceinline__ double dib_sti_logaddexp(double x, double y) {
-  const double m = x > y ? x : y;
-  return m + log(exp(x - m) + exp(y - m));
+// log-sum-exp over the data rows of probe i of group g: its splits in split order
+__device__ __forceinline__ double dib_sti_data_lse(const DibStiArgs& a, int g, int i) {
+  const double2 p = dib_lse_of_splits(a.part, a.S, (long long)a.G * a.npad, (long long)g * a.npad + i);
+  return dib_lse_value(p.x, p.y);
 }
 
 // map mode: one thread per probe; batches summed in order b = 0 .. nb-1, then / nb
@@ -279,9 +186,10 @@ dib_sti_combine_map_kernel(DibStiArgs a, double* __restrict__ lower, double* __r
   for (int b = 0; b < a.nb; ++b) {
     const int g = c * a.nb + b;
     const double l = a.lii[(long long)g * a.npad + p];
-    const double lse_d = dib_sti_lse_of(a, g, p);
-    lo += l - (dib_sti_logaddexp(l, lse_d) - log(N + 1.0));
-    up += l - (lse_d - log(N));
+    double li, ui;
+    dib_sandwich_pair(l, dib_sti_data_lse(a, g, p), log(N + 1.0), log(N), li, ui);
+    lo += li;
+    up += ui;
   }
   lower[i] = lo / (double)a.nb;
   upper[i] = up / (double)a.nb;
@@ -298,9 +206,8 @@ dib_sti_combine_sandwich_kernel(DibStiArgs a, double* __restrict__ lower_b, doub
   double lo = 0.0, up = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) {
     const double l = a.lii[(long long)g * a.npad + i];
-    const double lse_off = dib_sti_lse_of(a, g, i);
-    const double li = l - (dib_sti_logaddexp(l, lse_off) - logn);
-    const double ui = l - (lse_off - logn);
+    double li, ui;
+    dib_sandwich_pair(l, dib_sti_data_lse(a, g, i), logn, logn, li, ui);
     if (lower_rows) { lower_rows[(long long)g * n + i] = li; upper_rows[(long long)g * n + i] = ui; }
     lo += li;
     up += ui;

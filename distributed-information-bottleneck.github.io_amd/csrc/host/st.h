@@ -1,5 +1,5 @@
 // host/st.h - set-transformer building blocks (include/dib_st.h): softmax, Add + LayerNorm, the token chain, pooling, attention,
-// token KL, probe bounds, loss rows and the information maps (csrc/dib_st_info.h).
+// token KL and loss rows.  (The probe bounds and the information maps are in host/mi.h.)
 
 static int ln_grid(int64_t T, int D) { return grid_for(T, D <= 32 ? 8 : 4, 512); }
 
@@ -14,69 +14,6 @@ static size_t st_chain_bwd_lds(const dib_st_block_desc* d) {
   size_t fl = (size_t)DIB_SMALL_ROWS * (4 * dib_small_pitch(d->D) + 2 * d->D) + DIB_SMALL_XCH_FLOATS;
   for (int l = 0; l < d->n_ff; ++l) fl += 2 * (size_t)DIB_SMALL_ROWS * dib_small_pitch(d->ff_width[l]);
   return fl * sizeof(float);
-}
-
-// ---- information tracking of the set-transformer notebook (include/dib_st.h, csrc/dib_st_info.h) ----
-struct StiPlan {
-  int G = 0, tiles = 0, npad = 0, S = 1, rps = 0, rb = 0, emax = 0;
-  size_t lds = 0;
-  int64_t off_c = 0, off_part = 0, off_lii = 0, bytes = 0;
-};
-
-// grid and workspace of one dib_sti_bounds_kernel launch; false = outside the envelope
-static bool sti_plan(int sandwich, int n_probes, int chunk, int n_table_nbhd, int P, int E, int nb, int n_nbhd, StiPlan& p) {
-  if (E < 4 || E > 256 || (E & 3) || n_table_nbhd <= 0 || P <= 0 || nb <= 0 || n_nbhd <= 0) return false;
-  const int64_t N = (int64_t)n_nbhd * P, rows = (int64_t)n_table_nbhd * P;
-  if (N > (1 << 30) || rows > (1ll << 40)) return false;
-  int64_t cnt;
-  if (sandwich) {
-    if (N < 2) return false;
-    p.G = nb;
-    cnt = N;
-  } else {
-    if (n_probes <= 0 || chunk <= 0) return false;
-    const int64_t g = (int64_t)cdiv(n_probes, chunk) * nb;
-    if (g > 65535) return false;
-    p.G = (int)g;
-    cnt = std::min(chunk, n_probes);
-  }
-  if (p.G > 65535) return false;
-  p.npad = (int)((cnt + 63) / 64 * 64);
-  p.tiles = p.npad / 64;
-  p.emax = E <= 32 ? 32 : (E <= 64 ? 64 : 0);
-  p.rb = p.emax ? (E <= 32 ? 64 : 32) : (E <= 128 ? 16 : 4);
-  p.lds = (size_t)p.rb * E * 16 + (size_t)p.rb * 8 + (p.emax ? 0 : (size_t)64 * E * 8) + 4 * 64 * 16;
-  // row splits only where (probe tiles x groups) leave the chip short of workgroups; a function of the shape alone
-  const int64_t blocks = (int64_t)p.tiles * p.G;
-  int64_t S = std::max<int64_t>(1, std::min<int64_t>((2048 + blocks - 1) / blocks, (N + 255) / 256));
-  p.rps = (int)((N + S - 1) / S);
-  p.S = (int)((N + p.rps - 1) / p.rps);
-  p.off_c = align_up(rows * E * 2, 32);   // doubles
-  p.off_part = align_up(p.off_c + rows, 32);
-  p.off_lii = align_up(p.off_part + (int64_t)p.S * p.G * p.npad * 2, 32);
-  p.bytes = (p.off_lii + (int64_t)p.G * p.npad) * (int64_t)sizeof(double);
-  return true;
-}
-
-static int sti_launch(const StiPlan& p, DibStiArgs& a, int64_t rows, double* ws, hipStream_t st) {
-  a.tab = (const double2*)ws;
-  a.tab_c = ws + p.off_c;
-  a.part = (double2*)(ws + p.off_part);
-  a.lii = ws + p.off_lii;
-  a.G = p.G; a.S = p.S; a.npad = p.npad; a.rps = p.rps; a.rb = p.rb;
-  DIB_LAUNCH(dib_sti_table_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, st, a.enc_table, (long long)rows, a.E, a.lv_off,
-             (double2*)ws, ws + p.off_c);
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) return (int)e;
-  const dim3 grid(p.tiles, p.G, p.S);
-  if (p.emax == 32) {
-    DIB_LAUNCH(dib_sti_bounds_kernel<32>, grid, dim3(DIB_STI_THREADS), p.lds, st, a);
-  } else if (p.emax == 64) {
-    DIB_LAUNCH(dib_sti_bounds_kernel<64>, grid, dim3(DIB_STI_THREADS), p.lds, st, a);
-  } else {
-    // (the largest generic-path footprint - E = 256: 4 staged rows + the tile's samples - is 151 584 B, below the CU's 160 KB)
-    return launch_lds<&dib_sti_bounds_kernel<0>>(grid, dim3(DIB_STI_THREADS), p.lds, st, a);
-  }
-  return (int)hipGetLastError();
 }
 
 extern "C" {
@@ -376,42 +313,6 @@ int dib_token_reparam_kl_bwd(const float* enc_out, const float* g_u, const float
   return (int)hipGetLastError();
 }
 
-int64_t dib_mi_probe_workspace_bytes(int n_probes, int n_data, int E) {
-  if (n_probes <= 0 || n_data <= 0 || E <= 0) return DIB_E_ARG;
-  return (int64_t)sizeof(double) * ((4ll * E + 1) * ((int64_t)n_probes + n_data));   // per point set as dib_mi_workspace_bytes
-}
-
-int dib_mi_probe_bounds(const float* enc_probe, int n_probes, const float* enc_data, int n_data, int E, float logvar_offset,
-                        uint64_t seed, uint32_t step, uint32_t feature, double* lower_rows, double* upper_rows,
-                        double* u_probe_out, void* ws, dib_stream_t stream) {
-  if (!enc_probe || !enc_data || !lower_rows || !upper_rows || !ws || n_probes <= 0 || n_data <= 0 || E <= 0) return DIB_E_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  double* is_p = (double*)ws;
-  double* u_p = is_p + (int64_t)n_probes * E;
-  double* c_p = u_p + (int64_t)n_probes * E;
-  double* mut_p = c_p + n_probes;
-  double* ist_p = mut_p + (int64_t)n_probes * E;
-  double* is_d = ist_p + (int64_t)n_probes * E;
-  double* u_d = is_d + (int64_t)n_data * E;
-  double* c_d = u_d + (int64_t)n_data * E;
-  double* mut_d = c_d + n_data;
-  double* ist_d = mut_d + (int64_t)n_data * E;
-  DIB_LAUNCH(dib_mi_prep_kernel, dim3(cdiv(n_probes, 256)), dim3(256), 0, st, enc_probe, n_probes, E,
-                     (unsigned long long)seed, (unsigned)step, (unsigned)feature, is_p, u_p, c_p, mut_p, ist_p, logvar_offset);
-  DIB_LAUNCH(dib_mi_prep_kernel, dim3(cdiv(n_data, 256)), dim3(256), 0, st, enc_data, n_data, E,
-                     (unsigned long long)seed, (unsigned)step, (unsigned)feature + 1u, is_d, u_d, c_d, mut_d, ist_d, logvar_offset);
-  int rc = (int)hipGetLastError();
-  if (rc) return rc;
-  DIB_LAUNCH(dib_mi_probe_rows_kernel, dim3(n_probes), dim3(256), 0, st, enc_probe, (const double*)u_p,
-                     (const double*)is_p, (const double*)c_p, (const double*)mut_d, (const double*)ist_d, (const double*)c_d,
-                     n_data, E, lower_rows, upper_rows);
-  rc = (int)hipGetLastError();
-  if (rc) return rc;
-  if (u_probe_out)
-    return (int)hipMemcpyAsync(u_probe_out, u_p, (size_t)n_probes * E * sizeof(double), hipMemcpyDeviceToDevice, st);
-  return DIB_OK;
-}
-
 int64_t dib_loss_rows_workspace_bytes(int batch) {
   if (batch <= 0) return DIB_E_ARG;
   return (int64_t)cdiv(batch, 256) * 2 * (int64_t)sizeof(float);
@@ -428,55 +329,6 @@ int dib_loss_rows(int loss_kind, const float* pred, int out_dim, const float* y,
   int rc = (int)hipGetLastError();
   if (rc) return rc;
   DIB_LAUNCH(dib_loss_finalize_kernel, dim3(2), dim3(256), 0, st, (const float*)ws, blocks, (float)batch, out3);
-  return (int)hipGetLastError();
-}
-
-int64_t dib_mi_probe_map_workspace_bytes(int n_probes, int chunk, int n_table_nbhd, int P, int E, int nb, int n_nbhd) {
-  StiPlan p;
-  if (!sti_plan(0, n_probes, chunk, n_table_nbhd, P, E, nb, n_nbhd, p)) return DIB_E_ARG;
-  return p.bytes;
-}
-
-int dib_mi_probe_map(const float* enc_probe, int n_probes, int chunk, const float* enc_table, int n_table_nbhd, int P, int E,
-                     const int32_t* nbhd_idx, int nb, int n_nbhd, float logvar_offset, uint64_t seed, const uint32_t* steps,
-                     double* lower, double* upper, double* u_out, void* ws, dib_stream_t stream) {
-  StiPlan p;
-  if (!sti_plan(0, n_probes, chunk, n_table_nbhd, P, E, nb, n_nbhd, p)) return DIB_E_ARG;
-  if (!enc_probe || !enc_table || !nbhd_idx || !steps || !lower || !upper || !ws || ((uintptr_t)ws & 15)) return DIB_E_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  DibStiArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.enc_probe = enc_probe; a.enc_table = enc_table; a.nbhd = (const int*)nbhd_idx; a.steps = steps; a.u_out = u_out;
-  a.seed = (unsigned long long)seed; a.lv_off = logvar_offset; a.sandwich = 0; a.E = E; a.P = P; a.n_nbhd = n_nbhd;
-  a.n_table_nbhd = n_table_nbhd; a.M = n_probes; a.C = chunk; a.nb = nb; a.gstride = chunk;
-  int rc = sti_launch(p, a, (int64_t)n_table_nbhd * P, (double*)ws, st);
-  if (rc) return rc;
-  DIB_LAUNCH(dib_sti_combine_map_kernel, dim3(cdiv(n_probes, 256)), dim3(256), 0, st, a, lower, upper);
-  return (int)hipGetLastError();
-}
-
-int64_t dib_mi_sandwich_batched_workspace_bytes(int n_table_nbhd, int P, int E, int nb, int n_nbhd) {
-  StiPlan p;
-  if (!sti_plan(1, 0, 0, n_table_nbhd, P, E, nb, n_nbhd, p)) return DIB_E_ARG;
-  return p.bytes;
-}
-
-int dib_mi_sandwich_batched(const float* enc_table, int n_table_nbhd, int P, int E, const int32_t* nbhd_idx, int nb, int n_nbhd,
-                            float logvar_offset, uint64_t seed, uint32_t step, double* lower_batches, double* upper_batches,
-                            double* lower_rows, double* upper_rows, double* u_out, void* ws, dib_stream_t stream) {
-  StiPlan p;
-  if (!sti_plan(1, 0, 0, n_table_nbhd, P, E, nb, n_nbhd, p)) return DIB_E_ARG;
-  if (!enc_table || !nbhd_idx || !lower_batches || !upper_batches || !ws || ((uintptr_t)ws & 15)) return DIB_E_ARG;
-  if ((lower_rows == nullptr) != (upper_rows == nullptr)) return DIB_E_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  DibStiArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.enc_table = enc_table; a.nbhd = (const int*)nbhd_idx; a.u_out = u_out;
-  a.seed = (unsigned long long)seed; a.step0 = step; a.lv_off = logvar_offset; a.sandwich = 1; a.E = E; a.P = P;
-  a.n_nbhd = n_nbhd; a.n_table_nbhd = n_table_nbhd; a.nb = nb; a.gstride = n_nbhd * P;
-  int rc = sti_launch(p, a, (int64_t)n_table_nbhd * P, (double*)ws, st);
-  if (rc) return rc;
-  DIB_LAUNCH(dib_sti_combine_sandwich_kernel, dim3(nb), dim3(256), 0, st, a, lower_batches, upper_batches, lower_rows, upper_rows);
   return (int)hipGetLastError();
 }
 

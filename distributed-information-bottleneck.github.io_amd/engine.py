@@ -17,6 +17,7 @@ import torch
 
 from . import _lib
 from ._lib import ACTIVATIONS, LOSS_KINDS, check
+from .utils import mi_sandwich_rows
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -573,13 +574,7 @@ class HipEngine:
 
     def mi_sandwich_bounds(self, enc_out: torch.Tensor, seed: int, step: int, feature: int):
         """(InfoNCE lower, leave-one-out upper) in nats for one batch enc_out [N, 2E] (reference utils.py:36-62)."""
-        enc_out = self.to_device(enc_out)
-        n, e2 = enc_out.shape
-        ws = torch.empty(int(self.lib.dib_mi_workspace_bytes(n, e2 // 2)) // 8, dtype=torch.float64, device=self.device)
-        rows = torch.empty((2, n), dtype=torch.float64, device=self.device)
-        check(self.lib.dib_mi_sandwich_rows(_ptr(enc_out), n, e2 // 2, int(seed), int(step) & 0xFFFFFFFF, int(feature),
-                                            _ptr(rows[0]), _ptr(rows[1]), _ptr(ws), self._stream()),
-              "dib_mi_sandwich_rows")
+        rows = mi_sandwich_rows(self.lib, self.device, self.to_device(enc_out), seed, step, feature)
         m = rows.mean(dim=1).cpu().numpy()
         return float(m[0]), float(m[1])
 

@@ -66,9 +66,10 @@ def estimate_mi_sandwich_bounds(encoder, dataset, evaluation_batch_size=1024, nu
     bs = int(evaluation_batch_size)
     rng = np.random.default_rng(seed)
     if getattr(encoder, "_encoder", False):   # MeasurementIB.info_bott_encoder (chaos notebook cell 10): its [N, 2E] output
-        return _measurement_mi_bounds(encoder, x, n, bs, rng, int(number_evaluation_batches), seed)
-    if getattr(encoder, "_circuit", None) is not None:   # CircuitIB.feature_encoders[g] (Boolean-circuit notebook cell 4)
-        return _circuit_mi_bounds(encoder, x, n, bs, rng, int(number_evaluation_batches), seed)
+        return _encoder_mi_bounds(encoder, encoder._measurement, 0, x, n, bs, rng, int(number_evaluation_batches), seed)
+    if getattr(encoder, "_circuit", None) is not None:   # CircuitIB.feature_encoders[g] (Boolean-circuit notebook cell 4): one
+        # gate's [bs, 2] output, the per-gate form of CircuitIB.estimate_channel_mi_bounds' one-launch evaluation
+        return _encoder_mi_bounds(encoder, encoder._circuit, encoder.index, x, n, bs, rng, int(number_evaluation_batches), seed)
     model = encoder._model
     eng = model._ensure_engine()
     estimates = []
@@ -79,47 +80,32 @@ def estimate_mi_sandwich_bounds(encoder, dataset, evaluation_batch_size=1024, nu
     return np.mean(np.stack(estimates, 0), 0)
 
 
-def _measurement_mi_bounds(encoder, x, n, bs, rng, number_evaluation_batches, seed):
+def mi_sandwich_rows(lib, device, enc_out, seed, step, feature):
+    """dib_mi_sandwich_rows on one batch: enc_out is a float32 tensor [n, 2E] (mu | logvar) on `device`, the noise is keyed
+    (seed, step, row, feature).  Returns (lower_rows, upper_rows) in nats as the two rows of one float64 device tensor [2, n];
+    the launches go to the current stream and nothing waits for them."""
     import ctypes
 
     import torch
 
     from ._gemm_plan import _ptr
     from ._lib import check
-    m = encoder._measurement
+    enc_out = enc_out.contiguous()
+    n, e = enc_out.shape[0], enc_out.shape[1] // 2
+    ws = torch.empty(int(lib.dib_mi_workspace_bytes(n, e)) // 8 + 1, dtype=torch.float64, device=device)
+    rows = torch.empty((2, n), dtype=torch.float64, device=device)
+    check(lib.dib_mi_sandwich_rows(_ptr(enc_out), n, e, int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF, int(feature),
+                                   _ptr(rows[0]), _ptr(rows[1]), _ptr(ws),
+                                   ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "dib_mi_sandwich_rows")
+    return rows
+
+
+def _encoder_mi_bounds(encoder, m, feature, x, n, bs, rng, number_evaluation_batches, seed):
+    """batch by batch through mi_sandwich_rows on the output of a callable encoder owned by model `m` (its library and device)"""
     estimates = []
     for b in range(number_evaluation_batches):
         rows = rng.permutation(n)[:bs] if n >= bs else rng.integers(0, n, bs)
-        enc_out = encoder(x[rows])
-        e = enc_out.shape[1] // 2
-        ws = torch.empty(int(m.lib.dib_mi_workspace_bytes(bs, e)) // 8 + 1, dtype=torch.float64, device=m.device)
-        r = torch.empty((2, bs), dtype=torch.float64, device=m.device)
-        check(m.lib.dib_mi_sandwich_rows(_ptr(enc_out), bs, e, int(seed), b & 0xFFFFFFFF, 0, _ptr(r[0]), _ptr(r[1]), _ptr(ws),
-                                         ctypes.c_void_p(torch.cuda.current_stream(m.device).cuda_stream)), "dib_mi_sandwich_rows")
-        estimates.append(r.mean(dim=1).cpu().numpy())
-    return np.mean(np.stack(estimates, 0), 0)
-
-
-def _circuit_mi_bounds(encoder, x, n, bs, rng, number_evaluation_batches, seed):
-    """one gate's channel, batch by batch through dib_mi_sandwich_rows on its [bs, 2] output (noise feature = the gate index):
-    the per-gate form of CircuitIB.estimate_channel_mi_bounds' one-launch evaluation"""
-    import ctypes
-
-    import torch
-
-    from ._gemm_plan import _ptr
-    from ._lib import check
-    m = encoder._circuit
-    ws = torch.empty(int(m.lib.dib_mi_workspace_bytes(bs, 1)) // 8 + 1, dtype=torch.float64, device=m.device)
-    estimates = []
-    for b in range(number_evaluation_batches):
-        rows = rng.permutation(n)[:bs] if n >= bs else rng.integers(0, n, bs)
-        enc_out = encoder(x[rows]).contiguous()
-        r = torch.empty((2, bs), dtype=torch.float64, device=m.device)
-        check(m.lib.dib_mi_sandwich_rows(_ptr(enc_out), bs, 1, int(seed) & (2 ** 64 - 1), b & 0xFFFFFFFF, encoder.index,
-                                         _ptr(r[0]), _ptr(r[1]), _ptr(ws),
-                                         ctypes.c_void_p(torch.cuda.current_stream(m.device).cuda_stream)), "dib_mi_sandwich_rows")
-        estimates.append(r.mean(dim=1).cpu().numpy())
+        estimates.append(mi_sandwich_rows(m.lib, m.device, encoder(x[rows]), seed, b, feature).mean(dim=1).cpu().numpy())
     return np.mean(np.stack(estimates, 0), 0)
 
 

@@ -4,6 +4,7 @@ utils.estimate_mi_sandwich_bounds_from_parameters):
     samples against the Philox reference, across the envelope (E, rows, sample tiles, tables, groups, logvars, duplicates, row
     splits), with guard regions around every output; far-apart Gaussians; replay, split calls and refusals;
   - the parameter form of the sandwich bounds against the dib_mi_sandwich_rows loop, the oracle and the closed-form anchors;
+  - the Monte-Carlo terms of src_idx = arange(N) against the lower rows of the batched sandwich launch (one shared arithmetic);
   - a known answer (k independent bits through unit Gaussian noise) within 5 standard errors of the ORACLE's terms;
   - characterize: stacked launch = per-scale calls, launch count independent of scales and runs, the notebook's layout."""
 import ctypes
@@ -224,6 +225,39 @@ def test_bounds_from_parameters_equal_the_rows_loop_and_the_oracle():
         lo, up = osi.sandwich_rows_lse(mus[rows[b]].astype(np.float64), lvs[rows[b]].astype(np.float64), u[b])
         ref = np.array([lo.mean(), up.mean()]) / np.log(2.0)
         assert np.abs(est[b] - ref).max() < 1e-8 * (1 + np.abs(ref).max())
+
+
+def test_monte_carlo_terms_are_the_sandwich_lower_rows():
+    """The identity that makes the tiled families one family (csrc/dib_gauss_lse.h): with src_idx = arange(N) and one group,
+    dib_mi_monte_carlo's sample i is drawn from row i with the noise of dib_mi_sandwich_batched's batch arange(N) (P = 1, offset
+    0, same seed and step), so u_out is bit-equal and term_i = l_ii - (LSE_j l_ij - log N) = lower_i.
+    One table of N = 70 rows: the E <= 32 instantiations, a padded block of dimensions in the Monte-Carlo kernel (it stages 8)
+    and two staged blocks of rows (64 + 6: waves 0, 1 take a pair, waves 2, 3 the odd tail row).  E = 4, not 5:
+    dib_mi_sandwich_batched takes multiples of 4 only (asserted below), and 4 is the nearest size both entry points accept.
+    Tolerance (derived, not measured): the two sides differ in the float64 rounding of a 70-term log-sum-exp (the own term inside
+    or beside the streaming sum) and of l_ii (folded FMAs or (u - mu) / sigma) - a few ulp of values below 20, < 1e-13; the
+    assertion leaves two decades above that.  Observed on an MI355X: 2.7e-15 (profiles/mi_lse_equivalence.txt (C))."""
+    lib = _lib()
+    N, E, seed, step0 = 70, 4, 31, 9
+    assert lib.dib_mi_sandwich_batched_workspace_bytes(N, 1, 5, 1, N) < 0
+    rng = np.random.default_rng(70)
+    mu = 1.5 * rng.standard_normal((N, E))
+    lv = rng.uniform(-1.0, 0.5, (N, E))
+    table = np.concatenate([mu, lv], -1).astype(np.float32)
+    idx = np.arange(N)
+    _, terms, u_mc = _mc(lib, table[None], [0], idx[None], seed, step0)
+    tab_d = torch.tensor(table, device="cuda")
+    idx_d = torch.tensor(idx, dtype=torch.int32, device="cuda")
+    ws = torch.empty(int(lib.dib_mi_sandwich_batched_workspace_bytes(N, 1, E, 1, N)) // 8 + 2, dtype=torch.float64, device="cuda")
+    ob = torch.empty((2, 1), dtype=torch.float64, device="cuda")
+    rows = torch.empty((2, N), dtype=torch.float64, device="cuda")
+    u_sb = torch.empty((N, E), dtype=torch.float64, device="cuda")
+    assert lib.dib_mi_sandwich_batched(_p(tab_d), N, 1, E, _p(idx_d), 1, N, 0.0, seed, step0, _p(ob[0]), _p(ob[1]), _p(rows[0]),
+                                       _p(rows[1]), _p(u_sb), _p(ws), _st()) == 0
+    assert np.array_equal(u_sb.cpu().numpy(), u_mc[0])
+    diff = np.abs(rows[0].cpu().numpy() - terms[0]).max()
+    print(f"Monte-Carlo terms vs sandwich lower rows, N = {N}, E = {E}: max |difference| = {diff:.3e} nats")
+    assert diff <= 1e-11
 
 
 def test_bounds_from_parameters_reproduce_the_separation_zero_anchors():
