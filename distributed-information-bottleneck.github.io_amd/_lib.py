@@ -156,6 +156,7 @@ SIGNATURES = {
     "dib_launch_count": (c_int64, []),
     "dib_profile_enable": (c_int, [c_int]),
     "dib_profile_summary": (c_int, [POINTER(ctypes.c_double), POINTER(c_int)]),
+    "dib_profile_summary_n": (c_int, [POINTER(ctypes.c_double), POINTER(c_int), c_int]),
     "dib_gemm": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
                          c_void_p, c_int, c_int, c_void_p, c_void_p]),
 }
@@ -164,6 +165,8 @@ SIGNATURES = {
 SIGNATURES_ST = {
     "dib_gemm_grouped": (c_int, [c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_int, c_int, c_int, c_int64, c_void_p]),
+    "dib_wgrad_grouped": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                  c_int, c_int64, c_void_p]),
     "dib_reduce_splits": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p]),
     "dib_reduce_splits_add": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p]),
     "dib_gemm_skinny_k": (c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -23,9 +23,11 @@ inline int grid_for(int64_t n, int per_block = 256, int cap = 256 * 16) {
 
 // ---- optional live kernel timing (bench.py roofline): HIP events around every launch, on the launch stream ----
 // categories = kernel symbols: 0..11 dib_gemm_kernel<MODE,NI,NJ> at MODE*4 + (NI-1)*2 + (NJ-1); 12 fused encoder fwd;
-// 13 fused encoder bwd; 14 every other (HBM-bound) kernel; 15 dib_attn_fwd_kernel; 16 dib_attn_bwd_kernel
-constexpr int kProfCats = 17;
+// 13 fused encoder bwd; 14 every other (HBM-bound) kernel; 15 dib_attn_fwd_kernel; 16 dib_attn_bwd_kernel;
+// 17 / 18 dib_wgrad_stream_kernel on 128- / 64-column tiles (dib_profile_summary_n only: dib_profile_summary's arrays hold 17)
+constexpr int kProfCats = 19;
 constexpr int kProfFusedFwd = 12, kProfFusedBwd = 13, kProfOther = 14, kProfAttnFwd = 15, kProfAttnBwd = 16;
+constexpr int kProfWgradStream128 = 17, kProfWgradStream64 = 18;
 struct Prof {   // diagnostics (bench.py roofline): the tables are guarded, so a second thread's launches are recorded, not racy
   std::atomic<bool> on{false};
   std::mutex mu;
@@ -76,6 +78,10 @@ struct Tuning {
   int infonce_one_launch = 1; // dib_infonce_fwd_bwd at B <= 128, D <= 64 (dot-product similarities): one launch instead of three
   int attn_small_bwd_waves = 8;  // dib_attention_bwd for <= 64 particles: 8 waves (two per SIMD) or the 4-wave kernel
   int wgrad_flat_tile = 1;   // weight gradients with <= 32 rows and >= 256 columns on the 32 x 256 tile (0: 64 x 128, A/B)
+  int wgrad_stream = 1;      // weight gradients of 128-wide row-major operands in whole K-tiles on the LDS-free kernel
+                             // (dib_wgrad_stream.h; 0: the tiled kernel - bit-identical slabs) from ...
+  int wgrad_stream_rows = 8192;  // ... this many streamed rows up, when its wave-tiles (128 x 128 output tile x slab) fill ...
+  int wgrad_stream_fill = 85;    // ... this many percent of the chip's wave slots (four per CU) at least
   int attn_fwd_waves = 8;    // dib_attention_fwd for P >= 256: 8-wave workgroups of 256 queries sharing one staged K / V tile (4: the 4-wave
                              // kernel, which shorter sets always take; bit-identical outputs)
   int int_cluster_short_exchange = 1;  // clusters on one XCD exchange through that XCD's L2 (0: always the agent-scope protocol - the
@@ -154,6 +160,9 @@ static int* tuning_slot(const char* key) {
   if (!std::strcmp(key, "infonce_one_launch")) return &t.infonce_one_launch;
   if (!std::strcmp(key, "attn_small_bwd_waves")) return &t.attn_small_bwd_waves;
   if (!std::strcmp(key, "wgrad_flat_tile")) return &t.wgrad_flat_tile;
+  if (!std::strcmp(key, "wgrad_stream")) return &t.wgrad_stream;
+  if (!std::strcmp(key, "wgrad_stream_rows")) return &t.wgrad_stream_rows;
+  if (!std::strcmp(key, "wgrad_stream_fill")) return &t.wgrad_stream_fill;
   if (!std::strcmp(key, "wgrad_max_splits")) return &t.wgrad_max_splits;
   if (!std::strcmp(key, "num_cus")) return &t.num_cus;
   if (!std::strcmp(key, "attn_fwd_waves")) return &t.attn_fwd_waves;
@@ -209,10 +218,10 @@ int dib_profile_enable(int on) {
   return DIB_OK;
 }
 
-int dib_profile_summary(double* ms_by_category, int* launches_by_category) {
-  if (!ms_by_category || !launches_by_category) return DIB_E_ARG;
+int dib_profile_summary_n(double* ms_by_category, int* launches_by_category, int n) {
+  if (!ms_by_category || !launches_by_category || n < 0) return DIB_E_ARG;
   std::lock_guard<std::mutex> lk(g_prof.mu);
-  for (int c = 0; c < kProfCats; ++c) {
+  for (int c = 0; c < std::min(n, kProfCats); ++c) {
     double tot = 0.0;
     for (auto& sp : g_prof.spans[c]) {
       hipError_t e = hipEventSynchronize(sp.second);
@@ -225,7 +234,12 @@ int dib_profile_summary(double* ms_by_category, int* launches_by_category) {
     ms_by_category[c] = tot;
     launches_by_category[c] = (int)g_prof.spans[c].size();
   }
+  for (int c = kProfCats; c < n; ++c) { ms_by_category[c] = 0.0; launches_by_category[c] = 0; }
   return DIB_OK;
+}
+
+int dib_profile_summary(double* ms_by_category, int* launches_by_category) {
+  return dib_profile_summary_n(ms_by_category, launches_by_category, DIB_PROFILE_CATEGORIES);
 }
 
 }  // extern "C"

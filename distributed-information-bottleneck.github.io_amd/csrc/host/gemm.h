@@ -30,6 +30,61 @@ int launch_gemm_t(const DibGemmGroup* dev_groups, const GemmCall& c, int M, int 
   return (int)hipGetLastError();
 }
 
+// ---- the LDS-free weight gradient (csrc/dib_wgrad_stream.h) ----
+constexpr int kWgradStreamWavesPerCu = 4;   // one wave-tile per SIMD
+// What the kernel asks of a launch apart from its slab length: every group M % 128 == 0 and N == 64 (all groups) or
+// N % 128 == 0 (all groups), operands 16-byte aligned with lda / ldb multiples of 4, whole 64-row K-tiles.  Needs the groups on
+// the host: launches that only have the device table (dib_gemm_grouped) stay on the tiled kernel.
+static bool wgrad_stream_shape_ok(const DibGemmGroup* hg, int count, int batch, const float* A, const float* B, int* nt_out) {
+  if (!knobs().wgrad_stream || !hg || count <= 0) return false;
+  if ((((uintptr_t)A | (uintptr_t)B) & 15) != 0) return false;
+  int nt = 0;
+  for (int i = 0; i < count; ++i) {
+    const DibGemmGroup& g = hg[i];
+    const int M = g.M < 0 ? batch : g.M, N = g.N < 0 ? batch : g.N, K = g.K < 0 ? batch : g.K;
+    if (M <= 0 || (M & 127) || K <= 0 || (K & 63)) return false;
+    const int nt_g = N == 64 ? 2 : ((N > 0 && (N & 127) == 0) ? 4 : 0);
+    if (!nt_g || (nt && nt != nt_g)) return false;
+    nt = nt_g;
+    if (((g.a_off + g.a_boff * batch) | (g.b_off + g.b_boff * batch) | (long long)g.lda | (long long)g.ldb) & 3) return false;
+    if (g.lda < M || g.ldb < N) return false;
+  }
+  *nt_out = nt;
+  return true;
+}
+// ... and of its slabs: whole K-tiles, at least "wgrad_stream_rows" streamed rows, 32-bit byte offsets inside a slab - and
+// enough of them: a wave-tile is a whole 128 x 128 output tile of one slab, four per CU, so a launch with few tiles leaves
+// most SIMDs idle where the tiled kernel's smaller tiles fill them (the 256 x 256 integration layer at B = 65536: 4 tiles x 32
+// slabs = 128 waves; on this kernel it took as long as the 2048-wave encoder layer and the step lost 0.45 ms).  "wgrad_stream_fill":
+// the waves must fill this many percent of one round of the chip's wave slots.
+static bool wgrad_stream_slabs_ok(const DibGemmGroup* hg, int count, int batch, long long tiles, int nsplit, int rows_per_split) {
+  if (nsplit <= 0 || rows_per_split <= 0 || (long long)nsplit * rows_per_split < knobs().wgrad_stream_rows) return false;
+  if (tiles * nsplit * 100 < (long long)knobs().wgrad_stream_fill * split_rule_cus() * kWgradStreamWavesPerCu) return false;
+  for (int i = 0; i < count; ++i) {
+    const int K = hg[i].K < 0 ? batch : hg[i].K;
+    if ((rows_per_split & 63) && !(nsplit == 1 && rows_per_split >= K)) return false;
+    if (((long long)std::min(rows_per_split, K) + 8) * std::max(hg[i].lda, hg[i].ldb) * 4 >= (1ll << 31)) return false;
+  }
+  return true;
+}
+// NT: 4 = 128-column tiles, 2 = 64-column tiles; CH: the bias chains of the tiled kernel this launch replaces (dib_wgrad_stream.h)
+template <int NT, int CH>
+int launch_wgrad_stream(const DibGemmGroup* dev_groups, const GemmCall& c, int M, int N, const float* A, const float* B, float* C,
+                        float* bias_out, int batch, int nsplit, int rows_per_split, long long split_stride, hipStream_t st) {
+  const int tm = cdiv(M, 128), tn = cdiv(N, 32 * NT);
+  const long long waves = (long long)tm * tn * c.count * nsplit;
+  if (waves >= (1ll << 31)) return DIB_E_UNSUPPORTED;
+  ProfScope ps(NT == 4 ? kProfWgradStream128 : kProfWgradStream64, st);
+  const dim3 grid((unsigned)((waves + 3) / 4));
+  if ((long long)nsplit * rows_per_split >= knobs().stream_rows)   // the tiled kernels' cache policy of streamed operands
+    DIB_LAUNCH((dib_wgrad_stream_kernel<NT, CH, true>), grid, dim3(256), 0, st, dev_groups + c.first, A, B, C, bias_out, batch,
+               c.count, tm, tn, nsplit, rows_per_split, split_stride);
+  else
+    DIB_LAUNCH((dib_wgrad_stream_kernel<NT, CH, false>), grid, dim3(256), 0, st, dev_groups + c.first, A, B, C, bias_out, batch,
+               c.count, tm, tn, nsplit, rows_per_split, split_stride);
+  return (int)hipGetLastError();
+}
+
 // Batch-split count of one weight-gradient launch: `tiles` output tiles (all groups) x ns splits of rps batch rows on `slots`
 // co-resident workgroup slots (256 CUs x workgroups per CU of the tile shape).  Equal-length workgroups execute in
 // ceil(tiles ns / slots) rounds, so the launch takes ~ rounds x (rps + a fixed cost per workgroup).  The layout-wide rule - 32
@@ -77,7 +132,8 @@ static void pick_wgrad_splits(long long tiles, int slots, int K, int max_splits,
 template <int MODE>
 int launch_gemm(const DibGemmGroup* dev_groups, const GemmCall& c, const float* A, const float* B, float* C,
                 const float* bias, const float* aux, float* bias_out, int batch, int act, int nsplit, int rows_per_split,
-                long long split_stride, hipStream_t st, bool auto_split = false, int max_splits = 0, int* ns_used = nullptr) {
+                long long split_stride, hipStream_t st, bool auto_split = false, int max_splits = 0, int* ns_used = nullptr,
+                const DibGemmGroup* host_groups = nullptr) {
   if (ns_used) *ns_used = nsplit;
   if (c.count == 0) return DIB_OK;
   const int M = c.max_m < 0 ? batch : c.max_m;
@@ -97,6 +153,24 @@ int launch_gemm(const DibGemmGroup* dev_groups, const GemmCall& c, const float* 
     const long long wgs = (long long)cdiv(M, 128) * cdiv(N, 128) * nsplit * c.count;
     if (wgs < 256) ni1 = true;
     if (ni1 && !nj1 && (long long)cdiv(M, 64) * cdiv(N, 128) * nsplit * c.count < 128) nj1 = true;  // tiny batches
+  }
+  if constexpr (MODE == 2) {
+    // 128-wide row-major operands in whole K-tiles: global memory -> registers -> matrix cores, one 128 x 128 (128 x 64) tile per
+    // wave (dib_wgrad_stream.h; bit-identical slabs).  host_groups: this call's groups (c.first .. + count) as the host sees them.
+    int nt = 0;
+    if (wgrad_stream_shape_ok(host_groups, c.count, batch, A, B, &nt)) {
+      int ns = nsplit, rps = rows_per_split;
+      const long long tiles = (long long)cdiv(M, 128) * cdiv(N, 32 * nt) * c.count;
+      if (auto_split && ns > 1 && knobs().split_policy)
+        pick_wgrad_splits(tiles, split_rule_cus() * kWgradStreamWavesPerCu, batch, std::max(ns, max_splits), &ns, &rps);
+      if (wgrad_stream_slabs_ok(host_groups, c.count, batch, tiles, ns, rps)) {
+        if (ns_used) *ns_used = ns;
+        if (nt == 2) return launch_wgrad_stream<2, 4>(dev_groups, c, M, N, A, B, C, bias_out, batch, ns, rps, split_stride, st);
+        // (a 128-column launch the tile rule above would have put on 64-column tiles sums its bias the way those do)
+        return nj1 ? launch_wgrad_stream<4, 4>(dev_groups, c, M, N, A, B, C, bias_out, batch, ns, rps, split_stride, st)
+                   : launch_wgrad_stream<4, 2>(dev_groups, c, M, N, A, B, C, bias_out, batch, ns, rps, split_stride, st);
+      }
+    }
   }
   if (MODE == 2 && auto_split && nsplit > 1 && knobs().split_policy) {
     // co-resident workgroups per CU of each tile shape (LDS / register budget of dib_gemm_kernel<2, NI, NJ, BK>)
@@ -160,7 +234,7 @@ int launch_gemm(const dib_layout* l, const GemmCall& c, const float* A, const fl
   // 1 .. slab_count (the partial slabs the workspace holds)
   int ns_used = nsplit;
   int rc = launch_gemm<MODE>(l->dev_groups, c, A, B, C, bias, aux, bias_out, batch, act, nsplit, rows_per_split, split_stride,
-                             st, /*auto_split=*/MODE == 2, slab_count, &ns_used);
+                             st, /*auto_split=*/MODE == 2, slab_count, &ns_used, MODE == 2 ? l->table.data() + c.first : nullptr);
   if (MODE == 2 && rc == DIB_OK && slab_count > 1)
     rc = retire_stale_slabs(l, batch, l->table.data() + c.first, c.count, ns_used, slab_count, C, split_stride, st);
   return rc;
@@ -179,7 +253,7 @@ static int merged_wgrad(dib_layout* l, const dib_layout::WsMap& m, float* w, int
   const DibGemmGroup* dev = reinterpret_cast<const DibGemmGroup*>(w + m.wg_table) + first;
   int ns_used = m.nsplit;
   int rc = launch_gemm<2>(dev, c, w, w, gt, nullptr, nullptr, gt, batch, 0, m.nsplit, m.rows_per_split, align_up(l->n_params, 4), st,
-                          /*auto_split=*/true, m.nsplit, &ns_used);
+                          /*auto_split=*/true, m.nsplit, &ns_used, host.data() + first);
   if (rc == DIB_OK && m.nsplit > 1)
     rc = retire_stale_slabs(l, batch, host.data() + first, count, ns_used, m.nsplit, gt, align_up(l->n_params, 4), st);
   return rc;
@@ -230,6 +304,19 @@ int dib_gemm_grouped(int mode, int n_groups, const dib_gemm_desc* dev_desc, int 
     default: return launch_gemm<2>(g, c, A, B, C, nullptr, nullptr, bias_out, 0, 0, nsplit, rows_per_split,
                                    (long long)split_stride, st);
   }
+}
+
+int dib_wgrad_grouped(int n_groups, const dib_gemm_desc* dev_desc, const dib_gemm_desc* host_desc, int max_m, int max_n, int batch,
+                      const float* A, const float* B, float* C, float* bias_out, int nsplit, int rows_per_split,
+                      int64_t split_stride, dib_stream_t stream) {
+  if (!dev_desc || !host_desc || !A || !B || !C || n_groups <= 0 || max_m <= 0 || max_n <= 0 || batch < 0 || nsplit <= 0 ||
+      rows_per_split <= 0)
+    return DIB_E_ARG;
+  GemmCall c;
+  c.first = 0; c.count = n_groups; c.max_m = max_m; c.max_n = max_n;
+  return launch_gemm<2>(reinterpret_cast<const DibGemmGroup*>(dev_desc), c, A, B, C, nullptr, nullptr, bias_out, batch, 0, nsplit,
+                        rows_per_split, (long long)split_stride, (hipStream_t)stream, false, 0, nullptr,
+                        reinterpret_cast<const DibGemmGroup*>(host_desc));
 }
 
 int dib_gemm_skinny_k(int mode, int n_groups, const dib_gemm_desc* dev_desc, int M, int N, int K, const float* A,

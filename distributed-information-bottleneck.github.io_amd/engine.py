@@ -585,16 +585,17 @@ class HipEngine:
         return out
 
 
-PROFILE_CATEGORIES = 17  # include/dib_hip.h: DIB_PROFILE_CATEGORIES
+PROFILE_CATEGORIES = 19  # include/dib_hip.h: DIB_PROFILE_CATEGORIES_N (dib_profile_summary_n)
 
 
 def profile_summary(lib) -> dict:
     """{kernel symbol: (total ms, launches)} of the library's live HIP-event timing since dib_profile_enable(1)."""
     ms = (ctypes.c_double * PROFILE_CATEGORIES)()
     cnt = (c_int * PROFILE_CATEGORIES)()
-    check(lib.dib_profile_summary(ms, cnt), "dib_profile_summary")
+    check(lib.dib_profile_summary_n(ms, cnt, PROFILE_CATEGORIES), "dib_profile_summary_n")
     bk = lambda mode, ni, nj: 64 if (ni, nj) == (2, 2) or (mode, ni, nj) == (2, 1, 2) else 32  # csrc/host/gemm.h launch_gemm_t
     names = [f"dib_gemm_kernel<{mode}, {ni}, {nj}, {bk(mode, ni, nj)}>"
              for mode in (0, 1, 2) for ni in (1, 2) for nj in (1, 2)]
     names += ["dib_fused_encoder_fwd_kernel", "dib_fused_encoder_bwd_kernel", "other", "dib_attn_fwd_kernel", "dib_attn_bwd_kernel"]
+    names += ["dib_wgrad_stream_kernel<4>", "dib_wgrad_stream_kernel<2>"]   # 128- / 64-column tiles (csrc/dib_wgrad_stream.h)
     return {n: (float(ms[i]), int(cnt[i])) for i, n in enumerate(names) if cnt[i]}

@@ -264,6 +264,11 @@ int dib_step_tail(dib_layout* l, int batch, int part, int flags, float* params, 
  *                           first dib_workspace_bytes of a layout).  Fewer slabs shrink the tail's reduce but starve the small
  *                           weight gradients: 32 / 24 / 16 / 8 -> 8.20 / 8.27 / 8.38 / 8.57 ms per config-3 step (profiles/r06j_*)
  *   "wgrad_flat_tile" (1)   weight gradients of a <= 32-row operand against >= 256 columns use the 32 x 256 tile (0: 64 x 128)
+ *   "wgrad_stream"   (1)    weight gradients whose groups all have M % 128 == 0 and N == 64 or N % 128 == 0, 16-byte aligned operands
+ *                           with lda / ldb % 4 == 0 and slabs of whole 64-row K-tiles run on the LDS-free kernel of
+ *                           csrc/dib_wgrad_stream.h (0: the tiled kernel; the slabs are bit-identical) when they stream at least
+ *   "wgrad_stream_rows" (8192) this many rows and their (128 x 128 output tile, slab) pairs - one wave each, four per CU - fill
+ *   "wgrad_stream_fill" (85) this many percent of the chip's wave slots at least (few large tiles would leave SIMDs idle)
  *   "num_cus"        (0)    compute units the split rule prices rounds with; 0 = the calling thread's current device's own count
  *   "int_cluster"    (8)    the row-tile integration kernel puts each 16-row tile on this many co-resident workgroups, each a column
  *                           slice of every layer, slices exchanged through L2 (csrc/dib_small.h "cluster mode"; 0 / 1: one workgroup
@@ -387,6 +392,11 @@ int64_t dib_launch_count(void);
 #define DIB_PROFILE_CATEGORIES 17
 int dib_profile_enable(int on);
 int dib_profile_summary(double* ms_by_category /*[17]*/, int* launches_by_category /*[17]*/);
+/* The same into arrays of n entries (added within ABI 7; dib_profile_summary's arrays keep their 17): categories beyond 16 are
+ * 17 / 18 = dib_wgrad_stream_kernel on 128- / 64-column tiles (csrc/dib_wgrad_stream.h) - dib_profile_summary does not report
+ * them; entries beyond the library's categories come back zero. */
+#define DIB_PROFILE_CATEGORIES_N 19
+int dib_profile_summary_n(double* ms_by_category /*[n]*/, int* launches_by_category /*[n]*/, int n);
 
 /* ---- raw grouped GEMM (exposed for tests/benchmarks of the dominant kernel) ----------------
  * mode 0: C[M,N] = act(A[M,K] @ B[K,N] + bias)    mode 1: C[M,N] = (A[M,K] @ B[N,K]^T) * act'(aux)

@@ -40,6 +40,13 @@ typedef struct dib_gemm_desc {
 int dib_gemm_grouped(int mode, int n_groups, const dib_gemm_desc* dev_desc, int max_m, int max_n, const float* A,
                      const float* B, float* C, const float* bias, const float* aux, float* bias_out, int act, int nsplit,
                      int rows_per_split, int64_t split_stride, dib_stream_t stream);
+/* Mode 2 of dib_gemm_grouped for a caller that also has the descriptors on the HOST (host_desc[i] == dev_desc[i]) - what the
+ * library's own layouts have: the launch can then be checked for the LDS-free kernel (dib_set_tuning "wgrad_stream", dib_hip.h).
+ * *_boff are honoured here: an operand's offset is off + boff * batch (feature-major activations); M / N / K = -1 mean batch.
+ * Same slabs, bit for bit, whichever kernel runs.  (Added within ABI 7.) */
+int dib_wgrad_grouped(int n_groups, const dib_gemm_desc* dev_desc, const dib_gemm_desc* host_desc, int max_m, int max_n,
+                      int batch, const float* A, const float* B, float* C, float* bias_out, int nsplit, int rows_per_split,
+                      int64_t split_stride, dib_stream_t stream);
 int dib_reduce_splits(const float* partial, int64_t n, int nsplit, int64_t stride, float* out, dib_stream_t stream);
 /* out[i] += sum of the slabs (the split-K gradient of a residual branch added to the gradient already in `out`: one launch
  * instead of reduce + add) */

@@ -69,6 +69,9 @@ ORACLE_TESTS = {
     "test_gpu_mi_characterization.py": {
         "test_kernel_matches_oracle_across_the_envelope", "test_far_apart_gaussians_stay_finite",
         "test_bounds_from_parameters_equal_the_rows_loop_and_the_oracle", "test_known_answer_on_the_device"},
+    "test_gpu_wgrad_stream.py": {"test_stream_kernel_slabs_are_the_tiled_kernels_bit_for_bit",
+                                 "test_ineligible_shapes_stay_on_the_tiled_kernel",
+                                 "test_bias_chains_of_the_128_column_tiled_kernel"},
 }
 # tests that demand the bits (or fp32 summation-order tolerance) of a path the tests above check against an oracle
 EQUIVALENCE_TESTS = {
