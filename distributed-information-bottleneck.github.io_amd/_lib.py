@@ -100,6 +100,8 @@ SIGNATURES = {
     "dib_workspace_init": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "dib_workspace_offset": (c_int64, [c_void_p, c_int, c_int]),
     "dib_layout_wgrad_splits": (c_int, [c_void_p, c_int]),
+    "dib_workspace_h1_stashed": (c_int, [c_void_p, c_void_p]),
+    "dib_workspace_h1_materialize": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "dib_encoder_bank_fwd": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_uint64,
                                      c_uint32, c_int, c_void_p, c_void_p]),
     "dib_integration_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
@@ -301,7 +303,8 @@ def _attach(lib):
 
 
 def set_tuning(key: str, value: int) -> None:
-    """include/dib_hip.h dib_set_tuning: the library's only hidden inputs (it reads no environment variable)."""
+    """include/dib_hip.h dib_set_tuning: the library's only hidden inputs (it reads no environment variable).  The keys are
+    listed there; e.g. "wgrad_stream", "wgrad_recompute_h1" (read by the forward: set it before the step it is meant for)."""
     check(load_library().dib_set_tuning(key.encode(), int(value)), f"dib_set_tuning({key})")
 
 

@@ -20,6 +20,7 @@
 #include "dib_wgrad_stream.h"
 #include "dib_infonce_mfma.h"
 #include "dib_fused.h"
+#include "dib_wgrad_recompute.h"
 #include "dib_tail.h"
 #include "dib_small.h"
 #include "dib_st.h"

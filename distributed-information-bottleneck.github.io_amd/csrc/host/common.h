@@ -24,8 +24,11 @@ inline int grid_for(int64_t n, int per_block = 256, int cap = 256 * 16) {
 // ---- optional live kernel timing (bench.py roofline): HIP events around every launch, on the launch stream ----
 // categories = kernel symbols: 0..11 dib_gemm_kernel<MODE,NI,NJ> at MODE*4 + (NI-1)*2 + (NJ-1); 12 fused encoder fwd;
 // 13 fused encoder bwd; 14 every other (HBM-bound) kernel; 15 dib_attn_fwd_kernel; 16 dib_attn_bwd_kernel;
-// 17 / 18 dib_wgrad_stream_kernel on 128- / 64-column tiles (dib_profile_summary_n only: dib_profile_summary's arrays hold 17)
+// 17 / 18 dib_wgrad_stream_kernel on 128- / 64-column tiles (dib_profile_summary_n only: dib_profile_summary's arrays hold 17);
+// dib_wgrad_h1_kernel (dib_wgrad_recompute.h) is timed in 17 with the kernel it stands in for, and entry 19 of
+// dib_profile_summary_n reports which of 17's spans were its launches
 constexpr int kProfCats = 19;
+constexpr int kProfWgradH1Part = 19;
 constexpr int kProfFusedFwd = 12, kProfFusedBwd = 13, kProfOther = 14, kProfAttnFwd = 15, kProfAttnBwd = 16;
 constexpr int kProfWgradStream128 = 17, kProfWgradStream64 = 18;
 struct Prof {   // diagnostics (bench.py roofline): the tables are guarded, so a second thread's launches are recorded, not racy
@@ -33,6 +36,7 @@ struct Prof {   // diagnostics (bench.py roofline): the tables are guarded, so a
   std::mutex mu;
   std::vector<hipEvent_t> pool;                     // recycled events
   std::vector<std::pair<hipEvent_t, hipEvent_t>> spans[kProfCats];
+  std::vector<size_t> h1_spans;                     // indices into spans[kProfWgradStream128]: dib_wgrad_h1_kernel's launches
   hipEvent_t get() {
     if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
     hipEvent_t e = nullptr;
@@ -43,7 +47,8 @@ struct Prof {   // diagnostics (bench.py roofline): the tables are guarded, so a
 
 struct ProfScope {
   int cat; hipStream_t st; hipEvent_t a = nullptr, b = nullptr;
-  ProfScope(int c, hipStream_t s) : cat(c), st(s) {
+  bool h1_part;
+  ProfScope(int c, hipStream_t s, bool h1 = false) : cat(c), st(s), h1_part(h1) {
     // the small HBM-bound kernels are not bracketed (event pairs serialise kernel boundaries: ~10 us each); rocprofv3
     // reports them (profiles/*_kernel_stats.csv)
     if (g_prof.on.load(std::memory_order_relaxed) && cat != 14) {
@@ -52,7 +57,12 @@ struct ProfScope {
     }
   }
   ~ProfScope() {
-    if (a) { (void)hipEventRecord(b, st); std::lock_guard<std::mutex> lk(g_prof.mu); g_prof.spans[cat].push_back({a, b}); }
+    if (a) {
+      (void)hipEventRecord(b, st);
+      std::lock_guard<std::mutex> lk(g_prof.mu);
+      if (h1_part) g_prof.h1_spans.push_back(g_prof.spans[cat].size());
+      g_prof.spans[cat].push_back({a, b});
+    }
   }
 };
 
@@ -82,6 +92,9 @@ struct Tuning {
                              // (dib_wgrad_stream.h; 0: the tiled kernel - bit-identical slabs) from ...
   int wgrad_stream_rows = 8192;  // ... this many streamed rows up, when its wave-tiles (128 x 128 output tile x slab) fill ...
   int wgrad_stream_fill = 85;    // ... this many percent of the chip's wave slots (four per CU) at least
+  int wgrad_recompute_h1 = 1;    // fused encoder + that kernel for the layer-2 weight gradient + inputs <= 8 wide: the forward does not
+                                 // stash h1, the weight gradient recomputes it in registers (dib_wgrad_recompute.h; 0: stash and
+                                 // stream it - bit-identical gradients).  Read at the FORWARD; the backward follows its record
   int attn_fwd_waves = 8;    // dib_attention_fwd for P >= 256: 8-wave workgroups of 256 queries sharing one staged K / V tile (4: the 4-wave
                              // kernel, which shorter sets always take; bit-identical outputs)
   int int_cluster_short_exchange = 1;  // clusters on one XCD exchange through that XCD's L2 (0: always the agent-scope protocol - the
@@ -163,6 +176,7 @@ static int* tuning_slot(const char* key) {
   if (!std::strcmp(key, "wgrad_stream")) return &t.wgrad_stream;
   if (!std::strcmp(key, "wgrad_stream_rows")) return &t.wgrad_stream_rows;
   if (!std::strcmp(key, "wgrad_stream_fill")) return &t.wgrad_stream_fill;
+  if (!std::strcmp(key, "wgrad_recompute_h1")) return &t.wgrad_recompute_h1;
   if (!std::strcmp(key, "wgrad_max_splits")) return &t.wgrad_max_splits;
   if (!std::strcmp(key, "num_cus")) return &t.num_cus;
   if (!std::strcmp(key, "attn_fwd_waves")) return &t.attn_fwd_waves;
@@ -214,6 +228,7 @@ int dib_profile_enable(int on) {
     for (auto& sp : g_prof.spans[c]) { g_prof.pool.push_back(sp.first); g_prof.pool.push_back(sp.second); }
     g_prof.spans[c].clear();
   }
+  g_prof.h1_spans.clear();
   g_prof.on = on != 0;
   return DIB_OK;
 }
@@ -235,6 +250,18 @@ int dib_profile_summary_n(double* ms_by_category, int* launches_by_category, int
     launches_by_category[c] = (int)g_prof.spans[c].size();
   }
   for (int c = kProfCats; c < n; ++c) { ms_by_category[c] = 0.0; launches_by_category[c] = 0; }
+  if (n > kProfWgradH1Part) {   // the part of category 17 that ran dib_wgrad_h1_kernel
+    double tot = 0.0;
+    for (size_t i : g_prof.h1_spans) {
+      const auto& sp = g_prof.spans[kProfWgradStream128][i];
+      float ms = 0.f;   // (synchronised above)
+      hipError_t e = hipEventElapsedTime(&ms, sp.first, sp.second);
+      if (e != hipSuccess) return (int)e;
+      tot += ms;
+    }
+    ms_by_category[kProfWgradH1Part] = tot;
+    launches_by_category[kProfWgradH1Part] = (int)g_prof.h1_spans.size();
+  }
   return DIB_OK;
 }
 

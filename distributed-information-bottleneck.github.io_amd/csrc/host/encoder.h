@@ -21,6 +21,37 @@ static bool fused_bwd_ok(const dib_layout* l) {
   return true;
 }
 
+// Whether the training forward of this (layout, batch) may leave h1 unwritten because the layer-2 weight gradient will recompute it
+// (csrc/dib_wgrad_recompute.h), and the launch that weight gradient will then be.  Evaluated AT THE FORWARD and recorded per
+// workspace (dib_layout::h1_plan); the backward launches by the record, so a dib_set_tuning between the two calls cannot make it
+// read a stash that was not written.  All of: fused forward and backward of the 128-wide configuration, not the row-tile regime,
+// every feature's input at most 8 wide (one k-block of the forward's layer 1), the tuning key, and the layer-2 weight gradient of
+// this batch on the LDS-free kernel's 128-column tiles - the question launch_gemm<2> will ask (wgrad_stream_plan), with the
+// arguments encoder_bank_bwd_stages will pass.
+static bool use_small_enc(const dib_layout* l, int batch);
+static dib_layout::H1Plan h1_recompute_plan(const dib_layout* l, const dib_layout::WsMap& m, const float* w, int batch) {
+  dib_layout::H1Plan r;
+  if (!knobs().wgrad_recompute_h1 || l->fused_id != 0 || !fused_bwd_ok(l) || l->h1_side.empty() || !l->dev_h1_side) return r;
+  if (use_small_enc(l, batch)) return r;
+  const GemmCall& c = l->enc_wgrad[1];
+  WgradStreamPlan sp;
+  if (!wgrad_stream_plan(l->table.data() + c.first, c, w + m.enc_h[0], w + m.g_enc_h[1], batch, m.nsplit, m.rows_per_split,
+                         /*auto_split=*/true, m.nsplit, &sp) || sp.nt != 4)
+    return r;
+  r.recompute = true; r.ch = sp.ch; r.nsplit = sp.nsplit; r.rows_per_split = sp.rows_per_split;
+  return r;
+}
+static void h1_plan_record(const dib_layout* l, const void* ws, const dib_layout::H1Plan& p) {
+  std::lock_guard<std::mutex> lk(l->wg_mu);
+  if (p.recompute) l->h1_plan[ws] = p;
+  else l->h1_plan.erase(ws);   // (no entry = the stash is what the backward reads)
+}
+static dib_layout::H1Plan h1_plan_of(const dib_layout* l, const void* ws) {
+  std::lock_guard<std::mutex> lk(l->wg_mu);
+  auto it = l->h1_plan.find(ws);
+  return it == l->h1_plan.end() ? dib_layout::H1Plan() : it->second;
+}
+
 static int fused_encoder_fwd(dib_layout* l, const dib_layout::WsMap& m, float* w, const float* x, int64_t ldx,
                              const int32_t* row_idx, int64_t row0, int batch, const float* params, uint64_t seed,
                              uint32_t step, int deterministic, hipStream_t st, int* gx_out) {
@@ -34,6 +65,11 @@ static int fused_encoder_fwd(dib_layout* l, const dib_layout::WsMap& m, float* w
   a.h2mask = (unsigned long long*)(w + m.h2mask);
   a.h1mask = fused_bwd_ok(l) ? (unsigned long long*)(w + m.h1mask) : nullptr;
   if (deterministic & DIB_FWD_INFERENCE) { a.h1 = nullptr; a.h2 = nullptr; a.h2mask = nullptr; a.h1mask = nullptr; }  // no backward follows
+  else {   // the layer-2 weight gradient will recompute h1: only its act' bits are stashed
+    const dib_layout::H1Plan plan = h1_recompute_plan(l, m, w, batch);
+    h1_plan_record(l, w, plan);
+    if (plan.recompute) a.h1 = nullptr;
+  }
   a.step_dev = l->step_dev;
   const int gx = fused_gx(l, batch);
   *gx_out = gx;
@@ -189,6 +225,21 @@ static int encoder_bank_bwd_stages(dib_layout* l, int batch, const float* params
     const float* hin = ly == 0 ? w + m.P : w + m.enc_h[ly - 1];
     const bool wgrad_here = (last ? (stages & 2) : (stages & 1)) && !(fused && ly == 0);  // fused: d(W1|b1) comes out of the
                                                                                          // fused kernel, reduced at finalize
+    if (wgrad_here && ly == 1 && fused && !small) {
+      // Layer 2 after a forward that did not stash h1 (h1_recompute_plan): the recorded launch, h1 recomputed from P, W1 and b1.
+      // Under the staged data-parallel backward this is stage 1, like every front-layer weight gradient: it runs before any
+      // optimizer step touches W1, so the recompute sees the parameters the forward saw.
+      const dib_layout::H1Plan plan = h1_plan_of(l, ws);
+      if (plan.recompute) {
+        const GemmCall& c = l->enc_wgrad[ly];
+        rc = launch_wgrad_h1(plan.ch, l->act == 1, l->dev_groups, l->dev_h1_side, c, w + m.P, params, gout, gt, gt, batch, plan.nsplit,
+                             plan.rows_per_split, sstride, st);
+        if (rc == DIB_OK && m.nsplit > 1)
+          rc = retire_stale_slabs(l, batch, l->table.data() + c.first, c.count, plan.nsplit, m.nsplit, gt, sstride, st);
+        if (rc) return rc;
+        continue;   // (fused: no dgrad launch per layer)
+      }
+    }
     if (wgrad_here) {
       // narrow outputs (the 2E-wide last layer) run 128x64 tiles at 4 workgroups/CU: half as many, twice as long batch
       // splits fill the chip in one wave (measured 0.88 -> 0.71 ms); the unused slabs of these blocks stay zero.
@@ -220,6 +271,7 @@ int dib_encoder_bank_fwd(dib_layout* l, const float* x, int64_t ldx, const int32
   const auto m = l->map(batch);
   float* w = (float*)ws;
   if (use_small_enc(l, batch)) {   // gather + positional encoding + Dense chain + reparameterisation + KL partials: one launch
+    if (!(deterministic & DIB_FWD_INFERENCE)) h1_plan_record(l, ws, dib_layout::H1Plan());   // (this forward stashes h1)
     int rc = small_encoder_fwd(l, m, w, x, ldx, row_idx, row0, batch, params, seed, step, deterministic, st);
     if (rc || (deterministic & DIB_FWD_DEFER_SUMS)) return rc;
     ProfScope ps(kProfOther, st);
@@ -270,6 +322,18 @@ int dib_encoder_bank_bwd_stage(dib_layout* l, int batch, const float* params, fl
                                float inv_global_batch, int stage, void* ws, dib_stream_t stream) {
   if (stage != 1 && stage != 2) return DIB_E_ARG;
   return encoder_bank_bwd_stages(l, batch, params, grads, beta_dev, inv_global_batch, stage, ws, stream);
+}
+
+// A caller who wants to LOOK at the first hidden layer after a forward that left it to the weight gradient's recompute: write
+// DIB_WS_ENC_H0 + 0 now, from the workspace's P (the last forward's inputs) and `params`, with the grouped GEMM the unfused path
+// runs for this layer.  Not the fused forward's arithmetic: a value can differ from the one the step used in its last bit.
+int dib_workspace_h1_materialize(dib_layout* l, int batch, const float* params, void* ws, dib_stream_t stream) {
+  if (!l || !params || !ws || batch <= 0 || l->n_enc < 1) return DIB_E_ARG;
+  if (!l->dev_groups) return DIB_E_WORKSPACE;
+  const auto m = l->map(batch);
+  float* w = (float*)ws;
+  return launch_gemm<0>(l, l->enc_fwd[0], w + m.P, params, w + m.enc_h[0], params, nullptr, nullptr, batch, l->act, 1, 0, 0,
+                        (hipStream_t)stream);
 }
 
 // ---- evaluation helpers ------------------------------------------------------------------------------

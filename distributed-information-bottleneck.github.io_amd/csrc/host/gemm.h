@@ -129,6 +129,71 @@ static void pick_wgrad_splits(long long tiles, int slots, int K, int max_splits,
   *rps_out = brps;
 }
 
+// The tile rule of a weight gradient: narrow tiles for narrow outputs, and 64-row (then 64-column) tiles while 128 x 128 tiles x
+// splits do not fill 256 CUs (e.g. a 256 x 256 layer, tiny batches)
+static void wgrad_tile_rule(int M, int N, int nsplit, int count, bool* ni1, bool* nj1) {
+  *ni1 = M <= 64;
+  *nj1 = N <= 64;
+  if (!*ni1 && !*nj1) {
+    const long long wgs = (long long)cdiv(M, 128) * cdiv(N, 128) * nsplit * count;
+    if (wgs < 256) *ni1 = true;
+    if (*ni1 && !*nj1 && (long long)cdiv(M, 64) * cdiv(N, 128) * nsplit * count < 128) *nj1 = true;  // tiny batches
+  }
+}
+
+// Whether a weight-gradient launch goes to the LDS-free kernel, and how: nt = 4 / 2 (128- / 64-column tiles), ch = the bias chains
+// of the tiled kernel it replaces, the split it will run.  ONE question for the launch (launch_gemm<2>) and for whoever must know
+// its answer earlier (the fused forward deciding whether the layer-2 weight gradient will need the h1 stash, host/encoder.h).
+struct WgradStreamPlan { int nt = 0, ch = 0, nsplit = 0, rows_per_split = 0; };
+static bool wgrad_stream_plan(const DibGemmGroup* host_groups, const GemmCall& c, const float* A, const float* B, int batch, int nsplit,
+                              int rows_per_split, bool auto_split, int max_splits, WgradStreamPlan* plan) {
+  const int M = c.max_m < 0 ? batch : c.max_m, N = c.max_n < 0 ? batch : c.max_n;
+  int nt = 0;
+  if (c.count <= 0 || !wgrad_stream_shape_ok(host_groups, c.count, batch, A, B, &nt)) return false;
+  int ns = nsplit, rps = rows_per_split;
+  const long long tiles = (long long)cdiv(M, 128) * cdiv(N, 32 * nt) * c.count;
+  if (auto_split && ns > 1 && knobs().split_policy)
+    pick_wgrad_splits(tiles, split_rule_cus() * kWgradStreamWavesPerCu, batch, std::max(ns, max_splits), &ns, &rps);
+  if (!wgrad_stream_slabs_ok(host_groups, c.count, batch, tiles, ns, rps)) return false;
+  bool ni1, nj1;
+  wgrad_tile_rule(M, N, nsplit, c.count, &ni1, &nj1);
+  plan->nt = nt;
+  // (a 128-column launch the tile rule would have put on 64-column tiles sums its bias the way those do)
+  plan->ch = nt == 2 || nj1 ? 4 : 2;
+  plan->nsplit = ns;
+  plan->rows_per_split = rps;
+  return true;
+}
+
+// dib_wgrad_stream_kernel<4, CH, NTL>'s launch with the A operand recomputed (csrc/dib_wgrad_recompute.h): P, params and the
+// per-group side table instead of A.  ch: the bias chains (2 / 4); relu: the fused forward's RELU specialisation (act == 1)
+template <int CH, bool RELU>
+int launch_wgrad_h1_t(const DibGemmGroup* dev_groups, const DibWgradH1Side* dev_side, const GemmCall& c, int M, int N, const float* P,
+                      const float* params, const float* B, float* C, float* bias_out, int batch, int nsplit, int rows_per_split,
+                      long long split_stride, hipStream_t st) {
+  const int tm = cdiv(M, 128), tn = cdiv(N, 128);
+  const long long waves = (long long)tm * tn * c.count * nsplit;
+  if (waves >= (1ll << 31)) return DIB_E_UNSUPPORTED;
+  ProfScope ps(kProfWgradStream128, st, /*h1=*/true);   // timed with the kernel it stands in for
+  const dim3 grid((unsigned)((waves + 3) / 4));
+  if ((long long)nsplit * rows_per_split >= knobs().stream_rows)   // the tiled kernels' cache policy of streamed operands
+    DIB_LAUNCH((dib_wgrad_h1_kernel<CH, true, RELU>), grid, dim3(256), 0, st, dev_groups + c.first, dev_side, P, params, B, C,
+               bias_out, batch, c.count, tm, tn, nsplit, rows_per_split, split_stride);
+  else
+    DIB_LAUNCH((dib_wgrad_h1_kernel<CH, false, RELU>), grid, dim3(256), 0, st, dev_groups + c.first, dev_side, P, params, B, C,
+               bias_out, batch, c.count, tm, tn, nsplit, rows_per_split, split_stride);
+  return (int)hipGetLastError();
+}
+static int launch_wgrad_h1(int ch, bool relu, const DibGemmGroup* dev_groups, const DibWgradH1Side* dev_side, const GemmCall& c,
+                           const float* P, const float* params, const float* B, float* C, float* bias_out, int batch, int nsplit,
+                           int rows_per_split, long long split_stride, hipStream_t st) {
+#define DIB_GO(CH, RELU) launch_wgrad_h1_t<CH, RELU>(dev_groups, dev_side, c, c.max_m, c.max_n, P, params, B, C, bias_out, batch, nsplit, \
+                                                     rows_per_split, split_stride, st)
+  if (ch == 4) return relu ? DIB_GO(4, true) : DIB_GO(4, false);
+  return relu ? DIB_GO(2, true) : DIB_GO(2, false);
+#undef DIB_GO
+}
+
 template <int MODE>
 int launch_gemm(const DibGemmGroup* dev_groups, const GemmCall& c, const float* A, const float* B, float* C,
                 const float* bias, const float* aux, float* bias_out, int batch, int act, int nsplit, int rows_per_split,
@@ -148,28 +213,17 @@ int launch_gemm(const DibGemmGroup* dev_groups, const GemmCall& c, const float* 
     // dgrads measured no different and keep the round-1 threshold.
     if (ni1 && !nj1 && (long long)cdiv(M, 64) * cdiv(N, 128) * c.count < (MODE == 0 ? knobs().fwd_narrow_wgs : 128)) nj1 = true;
   }
-  if (MODE == 2 && !ni1 && !nj1) {
-    // small weight gradients (e.g. a 256x256 layer): 128x128 tiles x splits do not fill 256 CUs -> 64-row tiles
-    const long long wgs = (long long)cdiv(M, 128) * cdiv(N, 128) * nsplit * c.count;
-    if (wgs < 256) ni1 = true;
-    if (ni1 && !nj1 && (long long)cdiv(M, 64) * cdiv(N, 128) * nsplit * c.count < 128) nj1 = true;  // tiny batches
-  }
+  if (MODE == 2) wgrad_tile_rule(M, N, nsplit, c.count, &ni1, &nj1);
   if constexpr (MODE == 2) {
     // 128-wide row-major operands in whole K-tiles: global memory -> registers -> matrix cores, one 128 x 128 (128 x 64) tile per
     // wave (dib_wgrad_stream.h; bit-identical slabs).  host_groups: this call's groups (c.first .. + count) as the host sees them.
-    int nt = 0;
-    if (wgrad_stream_shape_ok(host_groups, c.count, batch, A, B, &nt)) {
-      int ns = nsplit, rps = rows_per_split;
-      const long long tiles = (long long)cdiv(M, 128) * cdiv(N, 32 * nt) * c.count;
-      if (auto_split && ns > 1 && knobs().split_policy)
-        pick_wgrad_splits(tiles, split_rule_cus() * kWgradStreamWavesPerCu, batch, std::max(ns, max_splits), &ns, &rps);
-      if (wgrad_stream_slabs_ok(host_groups, c.count, batch, tiles, ns, rps)) {
-        if (ns_used) *ns_used = ns;
-        if (nt == 2) return launch_wgrad_stream<2, 4>(dev_groups, c, M, N, A, B, C, bias_out, batch, ns, rps, split_stride, st);
-        // (a 128-column launch the tile rule above would have put on 64-column tiles sums its bias the way those do)
-        return nj1 ? launch_wgrad_stream<4, 4>(dev_groups, c, M, N, A, B, C, bias_out, batch, ns, rps, split_stride, st)
-                   : launch_wgrad_stream<4, 2>(dev_groups, c, M, N, A, B, C, bias_out, batch, ns, rps, split_stride, st);
-      }
+    WgradStreamPlan sp;
+    if (wgrad_stream_plan(host_groups, c, A, B, batch, nsplit, rows_per_split, auto_split, max_splits, &sp)) {
+      const int ns = sp.nsplit, rps = sp.rows_per_split;
+      if (ns_used) *ns_used = ns;
+      if (sp.nt == 2) return launch_wgrad_stream<2, 4>(dev_groups, c, M, N, A, B, C, bias_out, batch, ns, rps, split_stride, st);
+      return sp.ch == 4 ? launch_wgrad_stream<4, 4>(dev_groups, c, M, N, A, B, C, bias_out, batch, ns, rps, split_stride, st)
+                        : launch_wgrad_stream<4, 2>(dev_groups, c, M, N, A, B, C, bias_out, batch, ns, rps, split_stride, st);
     }
   }
   if (MODE == 2 && auto_split && nsplit > 1 && knobs().split_policy) {

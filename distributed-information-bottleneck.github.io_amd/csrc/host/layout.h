@@ -48,6 +48,12 @@ struct dib_layout {
   std::vector<int4> featmap;           // [F] {d_f, in_dim_f, x column, 0}
   const long long* dev_fused_offs = nullptr;
   const int4* dev_featmap = nullptr;
+  // the layer-2 weight gradient that recomputes h1 (dib_wgrad_recompute.h): its per-feature side table (empty: not applicable) and
+  // what the last training forward into each workspace decided - the backward launches by this record, never by the tuning table
+  struct H1Plan { bool recompute = false; int ch = 2, nsplit = 0, rows_per_split = 0; };
+  std::vector<DibWgradH1Side> h1_side;
+  const DibWgradH1Side* dev_h1_side = nullptr;
+  mutable std::map<const void*, H1Plan> h1_plan;   // by workspace (guarded by wg_mu)
   const unsigned* step_dev = nullptr;  // optional device-resident noise step (dib_layout_set_step_counter)
   // small-batch row-tile kernels (dib_small.h): which halves of the network they cover for this architecture
   bool sb_enc = false, sb_int = false;
@@ -324,6 +330,18 @@ int dib_layout_create(int F, const int* feature_dims, int n_enc, const int* enc_
     for (int ly = LE; ly < 3; ++ly)
       for (int f = 0; f < F; ++f) l->fused_offs.push_back(0);
     for (int f = 0; f < F; ++f) l->featmap.push_back(make_int4(l->dims[f], l->in_dim[f], l->x_off[f], l->in_off[f]));
+    // h1 = act(P W1 + b1) recomputed by the layer-2 weight gradient: the 128-wide fused configuration with inputs <= 8 wide (one
+    // k-block of the forward's layer 1)
+    bool in8 = true;
+    for (int f = 0; f < F; ++f) in8 = in8 && l->in_dim[f] <= 8;
+    if (l->fused_id == 0 && in8)
+      for (int f = 0; f < F; ++f) {
+        DibWgradH1Side sd;
+        std::memset(&sd, 0, sizeof(sd));
+        sd.p_boff = l->in_off[f]; sd.w1_off = l->enc_w_off[0][f]; sd.b1_off = l->enc_b_off[0][f];
+        sd.in_dim = l->in_dim[f]; sd.act = act;
+        l->h1_side.push_back(sd);
+      }
   }
   // small-batch row-tile kernels (dib_small.h): two-hidden-layer encoders of widths % 16 == 0 (<= 1024, E <= 512) with inputs
   // <= 15 wide (the 16th row of the d(W1|b1) tile carries the bias gradient) whose forward AND backward tiles, wide exchange buffer
@@ -386,7 +404,8 @@ int64_t dib_layout_table_bytes(const dib_layout* l) {
   return align_up((int64_t)l->table.size() * sizeof(DibGemmGroup), 256) +
          align_up((int64_t)l->colmap.size() * sizeof(int4), 256) +
          align_up((int64_t)l->fused_offs.size() * sizeof(long long), 256) +
-         align_up((int64_t)l->featmap.size() * sizeof(int4), 256);
+         align_up((int64_t)l->featmap.size() * sizeof(int4), 256) +
+         align_up((int64_t)l->h1_side.size() * sizeof(DibWgradH1Side), 256);
 }
 
 int dib_layout_upload_tables(dib_layout* l, void* dev_tables, dib_stream_t stream) {
@@ -409,6 +428,12 @@ int dib_layout_upload_tables(dib_layout* l, void* dev_tables, dib_stream_t strea
   l->dev_colmap = (const int4*)cm;
   l->dev_fused_offs = (const long long*)fo;
   l->dev_featmap = (const int4*)fmp;
+  if (!l->h1_side.empty()) {
+    char* hs = fmp + align_up((int64_t)l->featmap.size() * sizeof(int4), 256);
+    e = hipMemcpyAsync(hs, l->h1_side.data(), l->h1_side.size() * sizeof(DibWgradH1Side), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return (int)e;
+    l->dev_h1_side = (const DibWgradH1Side*)hs;
+  }
   return DIB_OK;
 }
 
@@ -426,6 +451,7 @@ int64_t dib_workspace_bytes(const dib_layout* l, int batch) {
 int dib_workspace_init(const dib_layout* l, int batch, void* ws, dib_stream_t stream) {
   if (!l || !ws || batch <= 0) return DIB_E_ARG;
   const auto m = l->map(batch);
+  { std::lock_guard<std::mutex> lk(l->wg_mu); l->h1_plan.erase(ws); }   // a fresh workspace holds no forward's decision
   // the arrival counters of dib_step_tail (self-cleaning afterwards)
   hipError_t e0 = hipMemsetAsync((float*)ws + m.sync, 0, (size_t)DIB_TAIL_SYNC_WORDS * sizeof(unsigned), (hipStream_t)stream);
   if (e0 != hipSuccess) return (int)e0;
@@ -467,6 +493,13 @@ int64_t dib_workspace_offset(const dib_layout* l, int batch, int which) {
       else return DIB_E_ARG;
   }
   return o * (int64_t)sizeof(float);
+}
+
+int dib_workspace_h1_stashed(const dib_layout* l, const void* ws) {
+  if (!l || !ws) return DIB_E_ARG;
+  std::lock_guard<std::mutex> lk(l->wg_mu);
+  auto it = l->h1_plan.find(ws);
+  return it == l->h1_plan.end() || !it->second.recompute ? 1 : 0;
 }
 
 int dib_layout_wgrad_splits(const dib_layout* l, int batch) {

@@ -494,6 +494,17 @@ class HipEngine:
     def enc_h(self, batch: int, layer: int) -> torch.Tensor:
         """post-activation output of encoder hidden layer `layer` as stashed by the training forward: [F, B, units]."""
         w = self.enc_units[layer]
+        if layer == 0 and int(self.lib.dib_workspace_h1_stashed(self.layout, _ptr(self.workspace(batch)))) == 0:
+            # the last training forward left this layer to the weight gradient's recompute (dib_set_tuning "wgrad_recompute_h1"):
+            # the region holds no activations.  Fill it from the inputs that forward left in the workspace and the CURRENT
+            # parameters (the unfused path's GEMM: last-bit differences from the step's own values are possible) - or fail.
+            rc = int(self.lib.dib_workspace_h1_materialize(self.layout, batch, _ptr(self.params), _ptr(self.workspace(batch)),
+                                                           self._stream()))
+            if rc != 0:
+                raise _lib.DibError(f"enc_h(layer=0): the last forward of batch size {batch} did not stash the first hidden layer (its "
+                                    f"layer-2 weight gradient recomputes it) and it could not be recomputed here "
+                                    f"(dib_workspace_h1_materialize -> {rc}); dib_set_tuning('wgrad_recompute_h1', 0) before the "
+                                    f"forward keeps the stash")
         return self.ws_view(batch, _lib.WS_ENC_H0 + layer, batch * self.F * w).view(self.F, batch, w)
 
     def int_h(self, batch: int, layer: int) -> torch.Tensor:
@@ -585,7 +596,7 @@ class HipEngine:
         return out
 
 
-PROFILE_CATEGORIES = 19  # include/dib_hip.h: DIB_PROFILE_CATEGORIES_N (dib_profile_summary_n)
+PROFILE_CATEGORIES = 19  # include/dib_hip.h dib_profile_summary_n: the kernel categories (entry 19 there re-counts a part of 17)
 
 
 def profile_summary(lib) -> dict:

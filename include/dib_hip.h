@@ -80,7 +80,9 @@ enum { DIB_WS_U = 0,        /* [B, F*E]  sampled embeddings, models.py:108,122 *
        DIB_WS_STEP_OUT = 4, /* [F+3]     per-step scalars: KL_f local sums, task-loss sum, #correct, rows */
        DIB_WS_G_PRED = 5,   /* [B, out]  dL/dpred */
        DIB_WS_ENC_H0 = 16,  /* + l: [F][B][units_l] feature-major post-activation output of encoder hidden layer l (training
-                               forward only; the backward's act' choices are exactly `value > 0`) */
+                               forward only; the backward's act' choices are exactly `value > 0`).  Layer 0 is NOT written by a
+                               forward whose layer-2 weight gradient recomputes it (tuning key "wgrad_recompute_h1"): ask
+                               dib_workspace_h1_stashed before reading it, dib_workspace_h1_materialize to fill it */
        DIB_WS_INT_H0 = 32   /* + l: [B][units_l] post-activation output of integration hidden layer l */ };
 
 const char* dib_version(void);
@@ -130,6 +132,13 @@ int64_t dib_workspace_bytes(const dib_layout* l, int batch);
 int dib_workspace_init(const dib_layout* l, int batch, void* ws, dib_stream_t stream);
 int64_t dib_workspace_offset(const dib_layout* l, int batch, int which); /* byte offset, <0 on error */
 int dib_layout_wgrad_splits(const dib_layout* l, int batch);
+/* 1 if the last training forward of this layout into workspace `ws` stashed the first hidden layer (DIB_WS_ENC_H0 + 0), 0 if it
+ * left the region unwritten because the layer-2 weight gradient recomputes it; <0 on error.  (Added within ABI 7.) */
+int dib_workspace_h1_stashed(const dib_layout* l, const void* ws);
+/* ... and for a caller who wants to look at that layer anyway: writes DIB_WS_ENC_H0 + 0 of `ws` from the inputs the last forward
+ * left in it and `params` (pass the parameters that forward saw), with the grouped GEMM of the unfused path - not the fused
+ * forward's arithmetic, so a value may differ in its last bit from the one the step used.  (Added within ABI 7.) */
+int dib_workspace_h1_materialize(dib_layout* l, int batch, const float* params, void* ws, dib_stream_t stream);
 
 /* ---- forward -----------------------------------------------------------------------------
  * dib_encoder_bank_fwd replaces models.py:101-115: tf.split, PositionalEncoding.call (models.py:22-23),
@@ -269,6 +278,11 @@ int dib_step_tail(dib_layout* l, int batch, int part, int flags, float* params, 
  *                           csrc/dib_wgrad_stream.h (0: the tiled kernel; the slabs are bit-identical) when they stream at least
  *   "wgrad_stream_rows" (8192) this many rows and their (128 x 128 output tile, slab) pairs - one wave each, four per CU - fill
  *   "wgrad_stream_fill" (85) this many percent of the chip's wave slots at least (few large tiles would leave SIMDs idle)
+ *   "wgrad_recompute_h1" (1) where the fused encoder kernels run (128-128-32 encoders, inputs <= 8 wide, not the row-tile regime) and the
+ *                           layer-2 weight gradient takes that kernel's 128-column tiles, the forward does not stash the first hidden
+ *                           layer and the weight gradient recomputes it in registers from the inputs, W1 and b1 (csrc/
+ *                           dib_wgrad_recompute.h; 0: stash and stream it; bit-identical gradients).  Read by the FORWARD, which records
+ *                           its decision per workspace; the backward follows the record whatever the key says by then
  *   "num_cus"        (0)    compute units the split rule prices rounds with; 0 = the calling thread's current device's own count
  *   "int_cluster"    (8)    the row-tile integration kernel puts each 16-row tile on this many co-resident workgroups, each a column
  *                           slice of every layer, slices exchanged through L2 (csrc/dib_small.h "cluster mode"; 0 / 1: one workgroup
@@ -394,8 +408,10 @@ int dib_profile_enable(int on);
 int dib_profile_summary(double* ms_by_category /*[17]*/, int* launches_by_category /*[17]*/);
 /* The same into arrays of n entries (added within ABI 7; dib_profile_summary's arrays keep their 17): categories beyond 16 are
  * 17 / 18 = dib_wgrad_stream_kernel on 128- / 64-column tiles (csrc/dib_wgrad_stream.h) - dib_profile_summary does not report
- * them; entries beyond the library's categories come back zero. */
-#define DIB_PROFILE_CATEGORIES_N 19
+ * them; 19 = the PART of 17 that ran dib_wgrad_h1_kernel (csrc/dib_wgrad_recompute.h, the same launch with one operand
+ * recomputed: timed in 17 with the kernel it stands in for, and counted here a second time); entries beyond the library's
+ * categories come back zero. */
+#define DIB_PROFILE_CATEGORIES_N 20
 int dib_profile_summary_n(double* ms_by_category /*[n]*/, int* launches_by_category /*[n]*/, int n);
 
 /* ---- raw grouped GEMM (exposed for tests/benchmarks of the dominant kernel) ----------------
