@@ -32,6 +32,7 @@
 #include "dib_partition.h"
 #include "dib_st_info.h"
 #include "dib_mi_channel.h"
+#include "dib_input_grad.h"
 #include "../../include/dib_st.h"
 #include "../../include/dib_measure.h"
 #include "../../include/dib_circuit.h"
@@ -43,6 +44,7 @@
 #include "host/layout.h"
 #include "host/gemm.h"
 #include "host/encoder.h"
+#include "host/input_grad.h"
 #include "host/small.h"
 #include "host/step.h"
 #include "host/infonce.h"

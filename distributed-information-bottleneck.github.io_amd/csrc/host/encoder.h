@@ -270,6 +270,7 @@ int dib_encoder_bank_fwd(dib_layout* l, const float* x, int64_t ldx, const int32
   hipStream_t st = (hipStream_t)stream;
   const auto m = l->map(batch);
   float* w = (float*)ws;
+  { std::lock_guard<std::mutex> lk(l->wg_mu); l->fwd_training[ws] = !(deterministic & DIB_FWD_INFERENCE); }
   if (use_small_enc(l, batch)) {   // gather + positional encoding + Dense chain + reparameterisation + KL partials: one launch
     if (!(deterministic & DIB_FWD_INFERENCE)) h1_plan_record(l, ws, dib_layout::H1Plan());   // (this forward stashes h1)
     int rc = small_encoder_fwd(l, m, w, x, ldx, row_idx, row0, batch, params, seed, step, deterministic, st);

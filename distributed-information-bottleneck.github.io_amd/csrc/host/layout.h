@@ -54,6 +54,9 @@ struct dib_layout {
   std::vector<DibWgradH1Side> h1_side;
   const DibWgradH1Side* dev_h1_side = nullptr;
   mutable std::map<const void*, H1Plan> h1_plan;   // by workspace (guarded by wg_mu)
+  // whether the last forward into each workspace was a training forward (it wrote the stashes a backward and
+  // dib_encoder_bank_input_grad read); no entry = no forward since dib_workspace_init (guarded by wg_mu)
+  mutable std::map<const void*, bool> fwd_training;
   const unsigned* step_dev = nullptr;  // optional device-resident noise step (dib_layout_set_step_counter)
   // small-batch row-tile kernels (dib_small.h): which halves of the network they cover for this architecture
   bool sb_enc = false, sb_int = false;
@@ -451,7 +454,7 @@ int64_t dib_workspace_bytes(const dib_layout* l, int batch) {
 int dib_workspace_init(const dib_layout* l, int batch, void* ws, dib_stream_t stream) {
   if (!l || !ws || batch <= 0) return DIB_E_ARG;
   const auto m = l->map(batch);
-  { std::lock_guard<std::mutex> lk(l->wg_mu); l->h1_plan.erase(ws); }   // a fresh workspace holds no forward's decision
+  { std::lock_guard<std::mutex> lk(l->wg_mu); l->h1_plan.erase(ws); l->fwd_training.erase(ws); }   // a fresh workspace holds no forward's decision
   // the arrival counters of dib_step_tail (self-cleaning afterwards)
   hipError_t e0 = hipMemsetAsync((float*)ws + m.sync, 0, (size_t)DIB_TAIL_SYNC_WORDS * sizeof(unsigned), (hipStream_t)stream);
   if (e0 != hipSuccess) return (int)e0;

@@ -329,6 +329,16 @@ class HipEngine:
             self.step_tail(batch, -1, FIN | head | finish_flags | (_lib.TAIL_BUMP if optimizer and optimizer[0] == "adam" else 0),
                            inv_global_batch, optimizer=optimizer, metrics_acc=metrics_acc)
 
+    def input_grad(self, x: torch.Tensor, row_idx: Optional[torch.Tensor], row0: int, batch: int) -> torch.Tensor:
+        """dL/dx [batch, sum_d] of the loss whose parameter gradients the last backward of this batch size wrote (include/dib_hip.h
+        dib_encoder_bank_input_grad): call it after that backward, with the x / row_idx / row0 its training forward read.  Row b is
+        batch position b (x row row_idx[b] or row0 + b)."""
+        dx = torch.empty((batch, self.sum_d), dtype=torch.float32, device=self.device)
+        check(self.lib.dib_encoder_bank_input_grad(self.layout, _ptr(x), x.stride(0), _ptr(row_idx), int(row0), batch,
+                                                   _ptr(self.params), _ptr(self.workspace(batch)), _ptr(dx), dx.stride(0),
+                                                   self._stream()), "dib_encoder_bank_input_grad")
+        return dx
+
     def accumulate_metrics(self, batch: int, inv_global_batch: float) -> None:
         check(self.lib.dib_metrics_accumulate(self.layout, batch, _ptr(self.beta_dev), float(inv_global_batch),
                                               _ptr(self.metrics_acc), _ptr(self.workspace(batch)), self._stream()),

@@ -260,6 +260,11 @@ class DistributedIBNet:
             loss.backward()                       # runs the HIP backward kernels; fills model.flat_parameters.grad
             torch_optimizer.step()                # any torch.optim optimizer over [model.flat_parameters]
 
+        When `inputs` is a tensor that requires a gradient (the output of another torch module), backward() also fills its
+        gradient (dib_encoder_bank_input_grad); otherwise nothing extra is launched.  First derivatives only.  That gradient is
+        bit-reproducible except under `row_ids` that repeat a row: the batch positions of a row are summed by torch's index_add_
+        (atomic adds, an order that varies from run to run).
+
         `row_ids` (int tensor [B]) keys the noise per sample; default arange(B).  The batch-mean convention of the
         KL term matches the reference: the caller's loss should be a mean over the batch."""
         eng = self._ensure_engine()
@@ -580,7 +585,8 @@ class DistributedIBNet:
 
 class _DIBFunction(torch.autograd.Function):
     """torch.autograd bridge: forward = dib_encoder_bank_fwd + dib_integration_fwd, backward = the HIP backward
-    kernels with the caller's dL/dpred injected (engine.backward_from_pred_grad)."""
+    kernels with the caller's dL/dpred injected (engine.backward_from_pred_grad) and, when the inputs require a gradient (they are
+    another network's outputs), dL/dx from engine.input_grad.  First derivatives only: a double backward raises."""
 
     @staticmethod
     def forward(ctx, flat_params, model, x, idx, step):
@@ -588,6 +594,9 @@ class _DIBFunction(torch.autograd.Function):
         B = x.shape[0]
         eng.forward(x, idx, 0, B, model.noise_seed, step)
         ctx.model, ctx.idx, ctx.step, ctx.B = model, idx, step, B
+        ctx.want_dx = bool(ctx.needs_input_grad[2])
+        if ctx.want_dx:
+            ctx.save_for_backward(x)   # read again by the input gradient (x itself: the forward gathers from it)
         ctx.beta = float(model.beta.value())
         # the activations the backward kernels re-read live in the engine's workspace for B rows: remember which forward
         # wrote them so that backward() can refuse to run on a workspace another forward has overwritten since
@@ -596,6 +605,7 @@ class _DIBFunction(torch.autograd.Function):
         return eng.pred(B).clone(), (kl * ctx.beta).reshape(())
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, g_pred, g_kl):
         model = ctx.model
         eng = model._ensure_engine()
@@ -612,7 +622,42 @@ class _DIBFunction(torch.autograd.Function):
         eng.backward_from_pred_grad(g_pred.contiguous(), ctx.idx, 0, ctx.B, model.noise_seed, ctx.step,
                                     inv_global_batch=1.0 / ctx.B)
         eng.set_beta(float(model.beta.value()))
-        return eng.grads.clone(), None, None, None, None
+        gx = None
+        if ctx.want_dx:   # (dout already carries the KL path: beta was scaled by g_kl above)
+            x, = ctx.saved_tensors
+            gx = eng.input_grad(x, ctx.idx, 0, ctx.B)
+            if ctx.idx is not None:   # per batch position -> the rows of x they were gathered from
+                gx = torch.zeros_like(x).index_add_(0, ctx.idx.long(), gx)
+        return eng.grads.clone(), None, gx, None, None
+
+
+class DistributedIBModule(torch.nn.Module):
+    """A DistributedIBNet as a torch.nn.Module, for a model whose inputs come out of another torch module (the reference README's
+    "Data that isn't tabular": a subnetwork processes some features and its output is fed into DistributedIBNet):
+
+        dib = DistributedIBModule(DistributedIBNet([4], [128, 128], [256], 1))
+        pred, kl_loss = dib(subnetwork(raw))          # differentiable in dib's parameters AND in subnetwork's
+        (my_loss(pred, y) + kl_loss).backward(); torch_optimizer.step()
+
+    Its one nn.Parameter, `flat_parameters`, shares memory with the engine's flat parameter buffer, so an optimizer step is seen by
+    the kernels directly.  forward(x, row_ids=None) is DistributedIBNet.forward_autograd.  Needs a GPU: there is no CPU path."""
+
+    def __init__(self, net: "DistributedIBNet"):
+        super().__init__()
+        self.net = net
+        eng = net._ensure_engine()   # raises without a GPU
+        self.flat_parameters = torch.nn.Parameter(eng.params, requires_grad=True)
+        net._flat_leaf = self.flat_parameters   # what forward_autograd differentiates with respect to
+
+    def forward(self, x, row_ids=None):
+        eng = self.net._ensure_engine()
+        if self.flat_parameters.data_ptr() != eng.params.data_ptr():
+            # forward_autograd would differentiate with respect to a fresh leaf and this Parameter would silently get no gradient
+            raise RuntimeError("DistributedIBModule.flat_parameters no longer shares memory with the engine's parameter buffer "
+                               "(the module was moved or copied, or the engine's buffer was replaced): build a new "
+                               "DistributedIBModule(net)")
+        self.net._flat_leaf = self.flat_parameters   # (another wrapper, or net.flat_parameters before this one, may have set its own)
+        return self.net.forward_autograd(x, row_ids=row_ids)
 
 
 class InfoBottleneckAnnealingCallback(Callback):

@@ -212,6 +212,19 @@ int dib_backward(dib_layout* l, int batch, const float* params, float* grads, co
  * workspace (library noise or DIB_FWD_DETERMINISTIC). */
 int dib_encoder_bank_bwd(dib_layout* l, int batch, const float* params, float* grads, const float* beta_dev,
                          float inv_global_batch, void* ws, dib_stream_t stream);
+/* dib_encoder_bank_input_grad: dL/dx of the loss whose parameter gradients dib_backward / dib_encoder_bank_bwd write (the task loss
+ * or the caller's dL/dpred, plus beta * sum_f KL_f, with the step's inv_global_batch) - the first encoder layer's gradient toward its
+ * inputs and the backward of PositionalEncoding.call (models.py:22-23), for a model whose inputs are another network's outputs
+ * (the reference README's "Data that isn't tabular").  Call it after the backward of a TRAINING forward on the same workspace, with
+ * that forward's x / ldx / row_idx / row0 / batch and the parameters it saw:
+ *   dx[b, c] for b < batch, c < sum of the feature widths, row stride lddx >= that sum; row b is batch POSITION b (x row
+ *   row_idx[b] or row0 + b) - a caller whose row_idx repeats a row sums the positions itself.  Nothing outside is written.
+ * One launch (csrc/dib_input_grad.h), no atomics, bit-reproducible.  After the fused or the row-tile backward, which do not leave
+ * dL/d(layer-1 pre-activation) in memory, the layer-1 dgrad GEMM of the grouped path runs first (and dib_workspace_h1_materialize
+ * before it where the forward did not stash h1).  Returns DIB_E_WORKSPACE, with nothing written, when the last forward into `ws`
+ * was a DIB_FWD_INFERENCE one (or there was none since dib_workspace_init).  (Added within ABI 7.) */
+int dib_encoder_bank_input_grad(dib_layout* l, const float* x, int64_t ldx, const int32_t* row_idx, int64_t row0, int batch,
+                                const float* params, void* ws, float* dx, int64_t lddx, dib_stream_t stream);
 /* The same work in two stages, for the data-parallel caller that wants the encoder bank's gradients in two all-reduce
  * buckets: stage 1 = the gradient chain and every weight gradient except the last encoder layer's (then
  * dib_grads_finalize_part(2) and the all-reduce of part 2), stage 2 = the last layer's weight gradient, which needs nothing

@@ -73,6 +73,8 @@ ORACLE_TESTS = {
                                  "test_ineligible_shapes_stay_on_the_tiled_kernel",
                                  "test_bias_chains_of_the_128_column_tiled_kernel"},
     "test_gpu_wgrad_recompute.py": {"test_recompute_arm_has_the_stash_arms_bits", "test_two_bias_chains_of_the_large_launches"},
+    "test_gpu_input_grad.py": {"test_zoo_parity", "test_kernel_envelope", "test_grid_stride_rounds", "test_multi_tile_large_batch", "test_h1_not_stashed",
+                               "test_addressing_and_guard_bands", "test_composition_upstream_module_gets_the_float64_gradient"},
 }
 # tests that demand the bits (or fp32 summation-order tolerance) of a path the tests above check against an oracle
 EQUIVALENCE_TESTS = {
@@ -92,6 +94,7 @@ EQUIVALENCE_TESTS = {
     "test_gpu_concurrency.py": {"test_two_threads_two_streams_equal_the_serial_run"},
     "test_gpu_wgrad_recompute.py": {"test_gates_keep_the_stash_path", "test_staged_backward_equals_the_single_call",
                                     "test_the_backward_follows_the_forwards_record", "test_enc_h_view_is_filled_on_demand"},
+    "test_gpu_input_grad.py": {"test_bridge_returns_dx_and_leaves_the_parameter_gradients_alone"},
     "test_gpu_st_information.py": {
         "test_batched_sandwich_equals_the_per_batch_rows_loop", "test_probe_map_equals_the_probe_bounds_loop",
         "test_information_maps_equal_information_map", "test_replay_is_bit_identical_and_bad_arguments_are_refused",
