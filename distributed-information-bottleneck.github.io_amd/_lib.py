@@ -306,7 +306,8 @@ def _attach(lib):
 
 def set_tuning(key: str, value: int) -> None:
     """include/dib_hip.h dib_set_tuning: the library's only hidden inputs (it reads no environment variable).  The keys are
-    listed there; e.g. "wgrad_stream", "wgrad_recompute_h1" (read by the forward: set it before the step it is meant for)."""
+    listed there; e.g. "wgrad_stream", "gemm_stream", "gemm_stream_rows", "gemm_stream_fill", "wgrad_recompute_h1" (read by the
+    forward: set it before the step it is meant for)."""
     check(load_library().dib_set_tuning(key.encode(), int(value)), f"dib_set_tuning({key})")
 
 

@@ -17,6 +17,7 @@
 #include "dib_gauss_lse.h"
 #include "dib_mi_rows.h"
 #include "dib_gemm.h"
+#include "dib_gemm_stream.h"
 #include "dib_wgrad_stream.h"
 #include "dib_infonce_mfma.h"
 #include "dib_fused.h"

@@ -26,9 +26,11 @@ inline int grid_for(int64_t n, int per_block = 256, int cap = 256 * 16) {
 // 13 fused encoder bwd; 14 every other (HBM-bound) kernel; 15 dib_attn_fwd_kernel; 16 dib_attn_bwd_kernel;
 // 17 / 18 dib_wgrad_stream_kernel on 128- / 64-column tiles (dib_profile_summary_n only: dib_profile_summary's arrays hold 17);
 // dib_wgrad_h1_kernel (dib_wgrad_recompute.h) is timed in 17 with the kernel it stands in for, and entry 19 of
-// dib_profile_summary_n reports which of 17's spans were its launches
+// dib_profile_summary_n reports which of 17's spans were its launches; dib_gemm_stream_kernel<0 / 1> (dib_gemm_stream.h) likewise is
+// timed in 3 / 7 with the 128 x 128 tiled kernel it stands in for, and entries 20 / 21 report which of those spans were its launches
 constexpr int kProfCats = 19;
 constexpr int kProfWgradH1Part = 19;
+constexpr int kProfGemmStreamPart = 20;   // + MODE
 constexpr int kProfFusedFwd = 12, kProfFusedBwd = 13, kProfOther = 14, kProfAttnFwd = 15, kProfAttnBwd = 16;
 constexpr int kProfWgradStream128 = 17, kProfWgradStream64 = 18;
 struct Prof {   // diagnostics (bench.py roofline): the tables are guarded, so a second thread's launches are recorded, not racy
@@ -37,6 +39,7 @@ struct Prof {   // diagnostics (bench.py roofline): the tables are guarded, so a
   std::vector<hipEvent_t> pool;                     // recycled events
   std::vector<std::pair<hipEvent_t, hipEvent_t>> spans[kProfCats];
   std::vector<size_t> h1_spans;                     // indices into spans[kProfWgradStream128]: dib_wgrad_h1_kernel's launches
+  std::vector<size_t> gs_spans[2];                  // indices into spans[3] / spans[7]: dib_gemm_stream_kernel<0 / 1>'s launches
   hipEvent_t get() {
     if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
     hipEvent_t e = nullptr;
@@ -48,7 +51,8 @@ struct Prof {   // diagnostics (bench.py roofline): the tables are guarded, so a
 struct ProfScope {
   int cat; hipStream_t st; hipEvent_t a = nullptr, b = nullptr;
   bool h1_part;
-  ProfScope(int c, hipStream_t s, bool h1 = false) : cat(c), st(s), h1_part(h1) {
+  int gs_mode;   // 0 / 1: a dib_gemm_stream_kernel launch (cat = 3 / 7); -1: not
+  ProfScope(int c, hipStream_t s, bool h1 = false, int gs = -1) : cat(c), st(s), h1_part(h1), gs_mode(gs) {
     // the small HBM-bound kernels are not bracketed (event pairs serialise kernel boundaries: ~10 us each); rocprofv3
     // reports them (profiles/*_kernel_stats.csv)
     if (g_prof.on.load(std::memory_order_relaxed) && cat != 14) {
@@ -61,6 +65,7 @@ struct ProfScope {
       (void)hipEventRecord(b, st);
       std::lock_guard<std::mutex> lk(g_prof.mu);
       if (h1_part) g_prof.h1_spans.push_back(g_prof.spans[cat].size());
+      if (gs_mode >= 0) g_prof.gs_spans[gs_mode].push_back(g_prof.spans[cat].size());
       g_prof.spans[cat].push_back({a, b});
     }
   }
@@ -92,6 +97,10 @@ struct Tuning {
                              // (dib_wgrad_stream.h; 0: the tiled kernel - bit-identical slabs) from ...
   int wgrad_stream_rows = 8192;  // ... this many streamed rows up, when its wave-tiles (128 x 128 output tile x slab) fill ...
   int wgrad_stream_fill = 85;    // ... this many percent of the chip's wave slots (four per CU) at least
+  int gemm_stream = 1;       // forward / dgrad GEMMs of one group with M % 128 == 0, N % 128 == 0, K % 32 == 0 and a linear / relu / leaky
+                             // activation on the LDS-free kernel (dib_gemm_stream.h; 0: the tiled kernel - bit-identical outputs) from ...
+  int gemm_stream_rows = 8192;   // ... this many rows (M) up, when its wave-tiles (128 x 128 output tiles) fill ...
+  int gemm_stream_fill = 85;     // ... this many percent of the chip's wave slots (four per CU) at least
   int wgrad_recompute_h1 = 1;    // fused encoder + that kernel for the layer-2 weight gradient + inputs <= 8 wide: the forward does not
                                  // stash h1, the weight gradient recomputes it in registers (dib_wgrad_recompute.h; 0: stash and
                                  // stream it - bit-identical gradients).  Read at the FORWARD; the backward follows its record
@@ -176,6 +185,9 @@ static int* tuning_slot(const char* key) {
   if (!std::strcmp(key, "wgrad_stream")) return &t.wgrad_stream;
   if (!std::strcmp(key, "wgrad_stream_rows")) return &t.wgrad_stream_rows;
   if (!std::strcmp(key, "wgrad_stream_fill")) return &t.wgrad_stream_fill;
+  if (!std::strcmp(key, "gemm_stream")) return &t.gemm_stream;
+  if (!std::strcmp(key, "gemm_stream_rows")) return &t.gemm_stream_rows;
+  if (!std::strcmp(key, "gemm_stream_fill")) return &t.gemm_stream_fill;
   if (!std::strcmp(key, "wgrad_recompute_h1")) return &t.wgrad_recompute_h1;
   if (!std::strcmp(key, "wgrad_max_splits")) return &t.wgrad_max_splits;
   if (!std::strcmp(key, "num_cus")) return &t.num_cus;
@@ -229,6 +241,8 @@ int dib_profile_enable(int on) {
     g_prof.spans[c].clear();
   }
   g_prof.h1_spans.clear();
+  g_prof.gs_spans[0].clear();
+  g_prof.gs_spans[1].clear();
   g_prof.on = on != 0;
   return DIB_OK;
 }
@@ -261,6 +275,18 @@ int dib_profile_summary_n(double* ms_by_category, int* launches_by_category, int
     }
     ms_by_category[kProfWgradH1Part] = tot;
     launches_by_category[kProfWgradH1Part] = (int)g_prof.h1_spans.size();
+  }
+  for (int mode = 0; mode < 2 && n > kProfGemmStreamPart + mode; ++mode) {   // the parts of categories 3 / 7 that ran dib_gemm_stream_kernel
+    double tot = 0.0;
+    for (size_t i : g_prof.gs_spans[mode]) {
+      const auto& sp = g_prof.spans[mode * 4 + 3][i];
+      float ms = 0.f;   // (synchronised above)
+      hipError_t e = hipEventElapsedTime(&ms, sp.first, sp.second);
+      if (e != hipSuccess) return (int)e;
+      tot += ms;
+    }
+    ms_by_category[kProfGemmStreamPart + mode] = tot;
+    launches_by_category[kProfGemmStreamPart + mode] = (int)g_prof.gs_spans[mode].size();
   }
   return DIB_OK;
 }

@@ -85,6 +85,66 @@ int launch_wgrad_stream(const DibGemmGroup* dev_groups, const GemmCall& c, int M
   return (int)hipGetLastError();
 }
 
+// ---- the LDS-free forward / dgrad GEMM (csrc/dib_gemm_stream.h) ----
+// Whether a forward (mode 0) / dgrad (mode 1) launch goes to dib_gemm_stream_kernel, and with how many waves.  It takes ONE
+// group (the integration network's layers, dib_gemm) with M % 128 == 0, N % 128 == 0, K % 32 == 0, operands, output and mask
+// 16-byte aligned with leading dimensions that are multiples of 4, 32-bit byte offsets inside a tile's operand extents, a linear /
+// relu / leaky-relu activation - from "gemm_stream_rows" rows up, and only when its wave-tiles (128 x 128 output tiles) fill
+// "gemm_stream_fill" percent of one round of the chip's wave slots (four per CU): a launch with fewer tiles leaves SIMDs idle where
+// the tiled kernel's smaller tiles fill them.  Needs the group on the host (launches that only have the device table stay tiled).
+// Every layer it takes measured faster than the tiled kernel in every alternating pair of tools/gemm_stream_bench.hip
+// (profiles/HISTORY.md section 27).
+struct GemmStreamPlan { int tiles_m = 0, tiles_n = 0, nwaves = 0, kind = 0; };
+static bool gemm_stream_plan(int mode, const DibGemmGroup* hg, const GemmCall& c, const float* A, const float* B, const float* C,
+                             const float* bias, const float* aux, int batch, int act, GemmStreamPlan* plan) {
+  if (!knobs().gemm_stream || !hg || c.count != 1 || (mode != 0 && mode != 1)) return false;
+  if (!(act == 0 || act == 1 || act == 2 || act == 7)) return false;   // the activations its unrolled epilogue carries
+  const DibGemmGroup& g = hg[0];
+  const long long M = g.M < 0 ? batch : g.M, N = g.N < 0 ? batch : g.N, K = g.K < 0 ? batch : g.K;
+  if (M <= 0 || (M & 127) || N <= 0 || (N & 127) || K <= 0 || (K & 31)) return false;
+  if (M < knobs().gemm_stream_rows) return false;
+  const bool mask = mode == 1 && aux != nullptr && act != 0;
+  if ((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (mask ? (uintptr_t)aux : 0)) & 15) != 0) return false;
+  if (((g.a_off + g.a_boff * batch) | (g.b_off + g.b_boff * batch) | (g.c_off + g.c_boff * batch) | (long long)g.lda | (long long)g.ldb |
+       (long long)g.ldc) & 3)
+    return false;
+  if (mask && (((g.aux_off + g.aux_boff * batch) | (long long)g.ldaux) & 3)) return false;
+  if (g.lda < K || g.ldb < (mode == 0 ? N : K) || g.ldc < N || (mask && g.ldaux < N)) return false;
+  // a tile's extents: 128 rows of A, C and the mask; K rows (mode 0) / 128 rows (mode 1) of B
+  const long long ext = std::max({128ll * g.lda, (mode == 0 ? K : 128ll) * g.ldb, 128ll * g.ldc, mask ? 128ll * g.ldaux : 0ll});
+  if ((ext + 8) * 4 >= (1ll << 31)) return false;
+  const long long tm = M / 128, tn = N / 128, tiles = tm * tn;
+  if (tiles >= (1ll << 31)) return false;
+  const long long slots = (long long)split_rule_cus() * kWgradStreamWavesPerCu;
+  if (tiles * 100 < (long long)knobs().gemm_stream_fill * slots) return false;
+  plan->tiles_m = (int)tm;
+  plan->tiles_n = (int)tn;
+  plan->nwaves = (int)std::min(tiles, slots);   // one wave per SIMD; a wave walks tiles / nwaves (+ 1) consecutive tiles
+  plan->kind = mode == 0 ? (act == 0 ? 0 : (act == 1 ? 1 : 2)) : (mask ? 3 : 0);
+  return true;
+}
+template <int MODE>
+int launch_gemm_stream(const GemmStreamPlan& sp, const DibGemmGroup* dev_group, const DibGemmGroup& hg, const float* A, const float* B,
+                       float* C, const float* bias, const float* aux, int batch, int act, hipStream_t st) {
+  ProfScope ps(MODE * 4 + 3, st, false, MODE);   // timed with the 128 x 128 tiled kernel it stands in for
+  // launch_gemm_t's rule for the output: non-temporal stores for a streamed launch whose output cannot stay in the infinity cache
+  const long long M = hg.M < 0 ? batch : hg.M, N = hg.N < 0 ? batch : hg.N;
+  const int nts = M >= knobs().stream_rows && M * N * (long long)sizeof(float) >= (256ll << 20) ? 1 : 0;
+  const dim3 grid((unsigned)((sp.nwaves + 3) / 4));
+#define DIB_GO(KIND) DIB_LAUNCH((dib_gemm_stream_kernel<MODE, KIND>), grid, dim3(256), 0, st, dev_group, A, B, C, bias, aux, batch, act, \
+                                sp.tiles_m, sp.tiles_n, sp.nwaves, nts)
+  if constexpr (MODE == 0) {
+    if (sp.kind == 1) DIB_GO(1);
+    else if (sp.kind == 0) DIB_GO(0);
+    else DIB_GO(2);
+  } else {
+    if (sp.kind == 3) DIB_GO(3);
+    else DIB_GO(0);
+  }
+#undef DIB_GO
+  return (int)hipGetLastError();
+}
+
 // Batch-split count of one weight-gradient launch: `tiles` output tiles (all groups) x ns splits of rps batch rows on `slots`
 // co-resident workgroup slots (256 CUs x workgroups per CU of the tile shape).  Equal-length workgroups execute in
 // ceil(tiles ns / slots) rounds, so the launch takes ~ rounds x (rps + a fixed cost per workgroup).  The layout-wide rule - 32
@@ -214,6 +274,13 @@ int launch_gemm(const DibGemmGroup* dev_groups, const GemmCall& c, const float* 
     if (ni1 && !nj1 && (long long)cdiv(M, 64) * cdiv(N, 128) * c.count < (MODE == 0 ? knobs().fwd_narrow_wgs : 128)) nj1 = true;
   }
   if (MODE == 2) wgrad_tile_rule(M, N, nsplit, c.count, &ni1, &nj1);
+  if constexpr (MODE != 2) {
+    // one large group in whole 128 x 128 x 32 tiles: global memory -> registers -> matrix cores (dib_gemm_stream.h; bit-identical
+    // outputs).  host_groups: this call's group as the host sees it.
+    GemmStreamPlan gp;
+    if (gemm_stream_plan(MODE, host_groups, c, A, B, C, bias, aux, batch, act, &gp))
+      return launch_gemm_stream<MODE>(gp, dev_groups + c.first, host_groups[0], A, B, C, bias, aux, batch, act, st);
+  }
   if constexpr (MODE == 2) {
     // 128-wide row-major operands in whole K-tiles: global memory -> registers -> matrix cores, one 128 x 128 (128 x 64) tile per
     // wave (dib_wgrad_stream.h; bit-identical slabs).  host_groups: this call's groups (c.first .. + count) as the host sees them.
@@ -288,7 +355,7 @@ int launch_gemm(const dib_layout* l, const GemmCall& c, const float* A, const fl
   // 1 .. slab_count (the partial slabs the workspace holds)
   int ns_used = nsplit;
   int rc = launch_gemm<MODE>(l->dev_groups, c, A, B, C, bias, aux, bias_out, batch, act, nsplit, rows_per_split, split_stride,
-                             st, /*auto_split=*/MODE == 2, slab_count, &ns_used, MODE == 2 ? l->table.data() + c.first : nullptr);
+                             st, /*auto_split=*/MODE == 2, slab_count, &ns_used, l->table.data() + c.first);
   if (MODE == 2 && rc == DIB_OK && slab_count > 1)
     rc = retire_stale_slabs(l, batch, l->table.data() + c.first, c.count, ns_used, slab_count, C, split_stride, st);
   return rc;
@@ -327,6 +394,15 @@ int dib_gemm(int mode, int M, int N, int K, const float* A, int lda, const float
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return (int)e;
   const int tm = cdiv(M, 128), tn = cdiv(N, 128);
   const DibGemmGroup* dg = (const DibGemmGroup*)dev_desc;
+  if (mode != 2) {   // a large product in whole tiles: the LDS-free kernel (dib_gemm_stream.h), bit-identical outputs
+    GemmCall c;
+    c.first = 0; c.count = 1; c.max_m = M; c.max_n = N;
+    GemmStreamPlan gp;
+    if (gemm_stream_plan(mode, &g, c, A, B, C, bias, aux, 0, act, &gp))
+      return mode == 0 ? launch_gemm_stream<0>(gp, dg, g, A, B, C, bias, aux, 0, act, st)
+                       : launch_gemm_stream<1>(gp, dg, g, A, B, C, bias, aux, 0, act, st);
+  }
+  ProfScope ps(mode * 4 + 3, st);
   const dim3 g1(8 * cdiv(tm, 8) * tn, 1, 1);
   if (mode == 0)
     DIB_LAUNCH((dib_gemm_kernel<0, 2, 2, 32>), g1, dim3(256), 0, st, dg, A, B, C, bias, aux, (float*)nullptr, 0,

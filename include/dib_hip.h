@@ -291,6 +291,12 @@ int dib_step_tail(dib_layout* l, int batch, int part, int flags, float* params, 
  *                           csrc/dib_wgrad_stream.h (0: the tiled kernel; the slabs are bit-identical) when they stream at least
  *   "wgrad_stream_rows" (8192) this many rows and their (128 x 128 output tile, slab) pairs - one wave each, four per CU - fill
  *   "wgrad_stream_fill" (85) this many percent of the chip's wave slots at least (few large tiles would leave SIMDs idle)
+ *   "gemm_stream"    (1)    forward / dgrad GEMMs of ONE group (the integration network's layers, dib_gemm) with M % 128 == 0,
+ *                           N % 128 == 0, K % 32 == 0, 16-byte aligned operands / output / mask with leading dimensions % 4 == 0 and a
+ *                           linear, relu or leaky-relu activation run on the LDS-free kernel of csrc/dib_gemm_stream.h (0: the tiled
+ *                           kernel; the outputs are bit-identical) when they have at least
+ *   "gemm_stream_rows" (8192) this many rows (M) and their 128 x 128 output tiles - one wave each, four per CU - fill
+ *   "gemm_stream_fill" (85) this many percent of the chip's wave slots at least (few large tiles would leave SIMDs idle)
  *   "wgrad_recompute_h1" (1) where the fused encoder kernels run (128-128-32 encoders, inputs <= 8 wide, not the row-tile regime) and the
  *                           layer-2 weight gradient takes that kernel's 128-column tiles, the forward does not stash the first hidden
  *                           layer and the weight gradient recomputes it in registers from the inputs, W1 and b1 (csrc/
@@ -422,9 +428,10 @@ int dib_profile_summary(double* ms_by_category /*[17]*/, int* launches_by_catego
 /* The same into arrays of n entries (added within ABI 7; dib_profile_summary's arrays keep their 17): categories beyond 16 are
  * 17 / 18 = dib_wgrad_stream_kernel on 128- / 64-column tiles (csrc/dib_wgrad_stream.h) - dib_profile_summary does not report
  * them; 19 = the PART of 17 that ran dib_wgrad_h1_kernel (csrc/dib_wgrad_recompute.h, the same launch with one operand
- * recomputed: timed in 17 with the kernel it stands in for, and counted here a second time); entries beyond the library's
- * categories come back zero. */
-#define DIB_PROFILE_CATEGORIES_N 20
+ * recomputed: timed in 17 with the kernel it stands in for, and counted here a second time); 20 / 21 = the PARTS of 3 / 7 that ran
+ * dib_gemm_stream_kernel<0 / 1> (csrc/dib_gemm_stream.h: timed with the 128 x 128 tiled forward / dgrad kernel it stands in for, and
+ * counted here a second time); entries beyond the library's categories come back zero. */
+#define DIB_PROFILE_CATEGORIES_N 22
 int dib_profile_summary_n(double* ms_by_category /*[n]*/, int* launches_by_category /*[n]*/, int n);
 
 /* ---- raw grouped GEMM (exposed for tests/benchmarks of the dominant kernel) ----------------

@@ -1,6 +1,6 @@
 """Kernel-coverage record of the GPU test suite.
 
-  on the GPU box (tools/runs/r06a.sh):
+  on the GPU box:
       DIB_COVERAGE_LOG=/tmp/cov/tests.tsv rocprofv3 --kernel-trace --marker-trace -M -f csv -d /tmp/cov/trace -- \
           python -m pytest tests -m gpu -q
       python tools/kernel_coverage.py build /tmp/cov/trace /tmp/cov/tests.tsv gpurun_out/r06_suite_kernel_coverage.txt
@@ -73,6 +73,9 @@ ORACLE_TESTS = {
                                  "test_ineligible_shapes_stay_on_the_tiled_kernel",
                                  "test_bias_chains_of_the_128_column_tiled_kernel"},
     "test_gpu_wgrad_recompute.py": {"test_recompute_arm_has_the_stash_arms_bits", "test_two_bias_chains_of_the_large_launches"},
+    "test_gpu_gemm_stream.py": {"test_forward_is_the_tiled_kernels_bit_for_bit", "test_dgrad_is_the_tiled_kernels_bit_for_bit",
+                                "test_padded_leading_dimensions", "test_output_of_256_mb_is_stored_non_temporally_with_the_same_bits",
+                                "test_ineligible_shapes_stay_on_the_tiled_kernel"},
     "test_gpu_input_grad.py": {"test_zoo_parity", "test_kernel_envelope", "test_grid_stride_rounds", "test_multi_tile_large_batch", "test_h1_not_stashed",
                                "test_addressing_and_guard_bands", "test_composition_upstream_module_gets_the_float64_gradient"},
 }
@@ -95,6 +98,7 @@ EQUIVALENCE_TESTS = {
     "test_gpu_wgrad_recompute.py": {"test_gates_keep_the_stash_path", "test_staged_backward_equals_the_single_call",
                                     "test_the_backward_follows_the_forwards_record", "test_enc_h_view_is_filled_on_demand"},
     "test_gpu_input_grad.py": {"test_bridge_returns_dx_and_leaves_the_parameter_gradients_alone"},
+    "test_gpu_gemm_stream.py": {"test_relu_mask_values", "test_whole_step_has_the_tiled_arms_bits"},
     "test_gpu_st_information.py": {
         "test_batched_sandwich_equals_the_per_batch_rows_loop", "test_probe_map_equals_the_probe_bounds_loop",
         "test_information_maps_equal_information_map", "test_replay_is_bit_identical_and_bad_arguments_are_refused",
