@@ -34,6 +34,8 @@ struct DibWgradH1Side {
 // One 8-row block of the bias chains (dib_wgrad_stream_kernel's, as a function): x = the running column sums of this block's chain, rb =
 // the block's four B rows of this lane.  Rows 8q .. 8q+3 are summed on the h = 0 side, handed over, rows 8q+4 .. 8q+7 on the
 // h = 1 side, handed back (meaningful on the h = 0 side only).
+// dib_wgrad_stream_kernel keeps its inline copy (and dib_wgh_epilogue's) on purpose: calling these from it changes the generated code of
+// all six instantiations (<4, 2, *>: 142 -> 144 VGPRs, 588 -> 590 loop instructions) - a GPU A/B first, not a clean-up (tools/isa_diff.py).
 template <int NT, typename FBV>
 __device__ __forceinline__ void dib_wgh_bias_block(FBV& xc, const FBV (&rb)[4]) {
   FBV y = xc;

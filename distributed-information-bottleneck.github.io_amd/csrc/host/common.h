@@ -33,13 +33,14 @@ constexpr int kProfWgradH1Part = 19;
 constexpr int kProfGemmStreamPart = 20;   // + MODE
 constexpr int kProfFusedFwd = 12, kProfFusedBwd = 13, kProfOther = 14, kProfAttnFwd = 15, kProfAttnBwd = 16;
 constexpr int kProfWgradStream128 = 17, kProfWgradStream64 = 18;
+// which kernel a span of category 17 / 3 / 7 timed: the category's own, or the one standing in for it (entries 19 / 20 / 21)
+enum ProfPart : unsigned char { kPartNone, kPartWgradH1, kPartGemmStreamFwd, kPartGemmStreamDgrad };
+struct ProfSpan { hipEvent_t a, b; ProfPart part; };
 struct Prof {   // diagnostics (bench.py roofline): the tables are guarded, so a second thread's launches are recorded, not racy
   std::atomic<bool> on{false};
   std::mutex mu;
   std::vector<hipEvent_t> pool;                     // recycled events
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> spans[kProfCats];
-  std::vector<size_t> h1_spans;                     // indices into spans[kProfWgradStream128]: dib_wgrad_h1_kernel's launches
-  std::vector<size_t> gs_spans[2];                  // indices into spans[3] / spans[7]: dib_gemm_stream_kernel<0 / 1>'s launches
+  std::vector<ProfSpan> spans[kProfCats];
   hipEvent_t get() {
     if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
     hipEvent_t e = nullptr;
@@ -50,9 +51,8 @@ struct Prof {   // diagnostics (bench.py roofline): the tables are guarded, so a
 
 struct ProfScope {
   int cat; hipStream_t st; hipEvent_t a = nullptr, b = nullptr;
-  bool h1_part;
-  int gs_mode;   // 0 / 1: a dib_gemm_stream_kernel launch (cat = 3 / 7); -1: not
-  ProfScope(int c, hipStream_t s, bool h1 = false, int gs = -1) : cat(c), st(s), h1_part(h1), gs_mode(gs) {
+  ProfPart part;
+  ProfScope(int c, hipStream_t s, ProfPart p = kPartNone) : cat(c), st(s), part(p) {
     // the small HBM-bound kernels are not bracketed (event pairs serialise kernel boundaries: ~10 us each); rocprofv3
     // reports them (profiles/*_kernel_stats.csv)
     if (g_prof.on.load(std::memory_order_relaxed) && cat != 14) {
@@ -64,9 +64,7 @@ struct ProfScope {
     if (a) {
       (void)hipEventRecord(b, st);
       std::lock_guard<std::mutex> lk(g_prof.mu);
-      if (h1_part) g_prof.h1_spans.push_back(g_prof.spans[cat].size());
-      if (gs_mode >= 0) g_prof.gs_spans[gs_mode].push_back(g_prof.spans[cat].size());
-      g_prof.spans[cat].push_back({a, b});
+      g_prof.spans[cat].push_back({a, b, part});
     }
   }
 };
@@ -237,12 +235,9 @@ int64_t dib_launch_count(void) { return (int64_t)g_dib_launches.load(std::memory
 int dib_profile_enable(int on) {
   std::lock_guard<std::mutex> lk(g_prof.mu);
   for (int c = 0; c < kProfCats; ++c) {
-    for (auto& sp : g_prof.spans[c]) { g_prof.pool.push_back(sp.first); g_prof.pool.push_back(sp.second); }
+    for (auto& sp : g_prof.spans[c]) { g_prof.pool.push_back(sp.a); g_prof.pool.push_back(sp.b); }
     g_prof.spans[c].clear();
   }
-  g_prof.h1_spans.clear();
-  g_prof.gs_spans[0].clear();
-  g_prof.gs_spans[1].clear();
   g_prof.on = on != 0;
   return DIB_OK;
 }
@@ -253,10 +248,10 @@ int dib_profile_summary_n(double* ms_by_category, int* launches_by_category, int
   for (int c = 0; c < std::min(n, kProfCats); ++c) {
     double tot = 0.0;
     for (auto& sp : g_prof.spans[c]) {
-      hipError_t e = hipEventSynchronize(sp.second);
+      hipError_t e = hipEventSynchronize(sp.b);
       if (e != hipSuccess) return (int)e;
       float ms = 0.f;
-      e = hipEventElapsedTime(&ms, sp.first, sp.second);
+      e = hipEventElapsedTime(&ms, sp.a, sp.b);
       if (e != hipSuccess) return (int)e;
       tot += ms;
     }
@@ -264,29 +259,24 @@ int dib_profile_summary_n(double* ms_by_category, int* launches_by_category, int
     launches_by_category[c] = (int)g_prof.spans[c].size();
   }
   for (int c = kProfCats; c < n; ++c) { ms_by_category[c] = 0.0; launches_by_category[c] = 0; }
-  if (n > kProfWgradH1Part) {   // the part of category 17 that ran dib_wgrad_h1_kernel
+  // the parts of categories 17 / 3 / 7 that ran dib_wgrad_h1_kernel / dib_gemm_stream_kernel<0> / <1>
+  static constexpr struct { int entry, cat; ProfPart part; } kParts[] = {{kProfWgradH1Part, kProfWgradStream128, kPartWgradH1},
+                                                                         {kProfGemmStreamPart, 3, kPartGemmStreamFwd},
+                                                                         {kProfGemmStreamPart + 1, 7, kPartGemmStreamDgrad}};
+  for (const auto& p : kParts) {
+    if (n <= p.entry) continue;
     double tot = 0.0;
-    for (size_t i : g_prof.h1_spans) {
-      const auto& sp = g_prof.spans[kProfWgradStream128][i];
+    int launches = 0;
+    for (const auto& sp : g_prof.spans[p.cat]) {
+      if (sp.part != p.part) continue;
       float ms = 0.f;   // (synchronised above)
-      hipError_t e = hipEventElapsedTime(&ms, sp.first, sp.second);
+      hipError_t e = hipEventElapsedTime(&ms, sp.a, sp.b);
       if (e != hipSuccess) return (int)e;
       tot += ms;
+      ++launches;
     }
-    ms_by_category[kProfWgradH1Part] = tot;
-    launches_by_category[kProfWgradH1Part] = (int)g_prof.h1_spans.size();
-  }
-  for (int mode = 0; mode < 2 && n > kProfGemmStreamPart + mode; ++mode) {   // the parts of categories 3 / 7 that ran dib_gemm_stream_kernel
-    double tot = 0.0;
-    for (size_t i : g_prof.gs_spans[mode]) {
-      const auto& sp = g_prof.spans[mode * 4 + 3][i];
-      float ms = 0.f;   // (synchronised above)
-      hipError_t e = hipEventElapsedTime(&ms, sp.first, sp.second);
-      if (e != hipSuccess) return (int)e;
-      tot += ms;
-    }
-    ms_by_category[kProfGemmStreamPart + mode] = tot;
-    launches_by_category[kProfGemmStreamPart + mode] = (int)g_prof.gs_spans[mode].size();
+    ms_by_category[p.entry] = tot;
+    launches_by_category[p.entry] = launches;
   }
   return DIB_OK;
 }

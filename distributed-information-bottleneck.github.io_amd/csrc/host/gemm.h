@@ -67,21 +67,26 @@ static bool wgrad_stream_slabs_ok(const DibGemmGroup* hg, int count, int batch, 
   }
   return true;
 }
+// The grid of its launches and of dib_wgrad_h1_kernel's: one wave per (128 x tile_n output tile, slab), four waves per workgroup;
+// ntl: operands loaded non-temporally - the tiled kernels' cache policy of streamed operands ("stream_rows")
+struct WgradWaveGrid { int tm, tn; dim3 grid; bool ntl; };
+static int wgrad_wave_grid(int M, int N, int tile_n, int count, int nsplit, int rows_per_split, WgradWaveGrid* w) {
+  const int tm = cdiv(M, 128), tn = cdiv(N, tile_n);
+  const long long waves = (long long)tm * tn * count * nsplit;
+  if (waves >= (1ll << 31)) return DIB_E_UNSUPPORTED;
+  *w = {tm, tn, dim3((unsigned)((waves + 3) / 4)), (long long)nsplit * rows_per_split >= knobs().stream_rows};
+  return DIB_OK;
+}
 // NT: 4 = 128-column tiles, 2 = 64-column tiles; CH: the bias chains of the tiled kernel this launch replaces (dib_wgrad_stream.h)
 template <int NT, int CH>
 int launch_wgrad_stream(const DibGemmGroup* dev_groups, const GemmCall& c, int M, int N, const float* A, const float* B, float* C,
                         float* bias_out, int batch, int nsplit, int rows_per_split, long long split_stride, hipStream_t st) {
-  const int tm = cdiv(M, 128), tn = cdiv(N, 32 * NT);
-  const long long waves = (long long)tm * tn * c.count * nsplit;
-  if (waves >= (1ll << 31)) return DIB_E_UNSUPPORTED;
+  WgradWaveGrid w;
+  if (int rc = wgrad_wave_grid(M, N, 32 * NT, c.count, nsplit, rows_per_split, &w)) return rc;
   ProfScope ps(NT == 4 ? kProfWgradStream128 : kProfWgradStream64, st);
-  const dim3 grid((unsigned)((waves + 3) / 4));
-  if ((long long)nsplit * rows_per_split >= knobs().stream_rows)   // the tiled kernels' cache policy of streamed operands
-    DIB_LAUNCH((dib_wgrad_stream_kernel<NT, CH, true>), grid, dim3(256), 0, st, dev_groups + c.first, A, B, C, bias_out, batch,
-               c.count, tm, tn, nsplit, rows_per_split, split_stride);
-  else
-    DIB_LAUNCH((dib_wgrad_stream_kernel<NT, CH, false>), grid, dim3(256), 0, st, dev_groups + c.first, A, B, C, bias_out, batch,
-               c.count, tm, tn, nsplit, rows_per_split, split_stride);
+  const auto kernel = w.ntl ? dib_wgrad_stream_kernel<NT, CH, true> : dib_wgrad_stream_kernel<NT, CH, false>;
+  DIB_LAUNCH(kernel, w.grid, dim3(256), 0, st, dev_groups + c.first, A, B, C, bias_out, batch, c.count, w.tm, w.tn, nsplit,
+             rows_per_split, split_stride);
   return (int)hipGetLastError();
 }
 
@@ -123,12 +128,15 @@ static bool gemm_stream_plan(int mode, const DibGemmGroup* hg, const GemmCall& c
   plan->kind = mode == 0 ? (act == 0 ? 0 : (act == 1 ? 1 : 2)) : (mask ? 3 : 0);
   return true;
 }
+// {whether the plan took the call, the launch's return code}; dev_group / hg: the call's one group on the device / on the host
 template <int MODE>
-int launch_gemm_stream(const GemmStreamPlan& sp, const DibGemmGroup* dev_group, const DibGemmGroup& hg, const float* A, const float* B,
-                       float* C, const float* bias, const float* aux, int batch, int act, hipStream_t st) {
-  ProfScope ps(MODE * 4 + 3, st, false, MODE);   // timed with the 128 x 128 tiled kernel it stands in for
+std::pair<bool, int> try_gemm_stream(const DibGemmGroup* dev_group, const DibGemmGroup* hg, const GemmCall& c, const float* A, const float* B,
+                                     float* C, const float* bias, const float* aux, int batch, int act, hipStream_t st) {
+  GemmStreamPlan sp;
+  if (!gemm_stream_plan(MODE, hg, c, A, B, C, bias, aux, batch, act, &sp)) return {false, DIB_OK};
+  ProfScope ps(MODE * 4 + 3, st, MODE == 0 ? kPartGemmStreamFwd : kPartGemmStreamDgrad);   // timed with the tiled kernel it stands in for
   // launch_gemm_t's rule for the output: non-temporal stores for a streamed launch whose output cannot stay in the infinity cache
-  const long long M = hg.M < 0 ? batch : hg.M, N = hg.N < 0 ? batch : hg.N;
+  const long long M = hg->M < 0 ? batch : hg->M, N = hg->N < 0 ? batch : hg->N;
   const int nts = M >= knobs().stream_rows && M * N * (long long)sizeof(float) >= (256ll << 20) ? 1 : 0;
   const dim3 grid((unsigned)((sp.nwaves + 3) / 4));
 #define DIB_GO(KIND) DIB_LAUNCH((dib_gemm_stream_kernel<MODE, KIND>), grid, dim3(256), 0, st, dev_group, A, B, C, bias, aux, batch, act, \
@@ -142,7 +150,7 @@ int launch_gemm_stream(const GemmStreamPlan& sp, const DibGemmGroup* dev_group, 
     else DIB_GO(0);
   }
 #undef DIB_GO
-  return (int)hipGetLastError();
+  return {true, (int)hipGetLastError()};
 }
 
 // Batch-split count of one weight-gradient launch: `tiles` output tiles (all groups) x ns splits of rps batch rows on `slots`
@@ -231,17 +239,12 @@ template <int CH, bool RELU>
 int launch_wgrad_h1_t(const DibGemmGroup* dev_groups, const DibWgradH1Side* dev_side, const GemmCall& c, int M, int N, const float* P,
                       const float* params, const float* B, float* C, float* bias_out, int batch, int nsplit, int rows_per_split,
                       long long split_stride, hipStream_t st) {
-  const int tm = cdiv(M, 128), tn = cdiv(N, 128);
-  const long long waves = (long long)tm * tn * c.count * nsplit;
-  if (waves >= (1ll << 31)) return DIB_E_UNSUPPORTED;
-  ProfScope ps(kProfWgradStream128, st, /*h1=*/true);   // timed with the kernel it stands in for
-  const dim3 grid((unsigned)((waves + 3) / 4));
-  if ((long long)nsplit * rows_per_split >= knobs().stream_rows)   // the tiled kernels' cache policy of streamed operands
-    DIB_LAUNCH((dib_wgrad_h1_kernel<CH, true, RELU>), grid, dim3(256), 0, st, dev_groups + c.first, dev_side, P, params, B, C,
-               bias_out, batch, c.count, tm, tn, nsplit, rows_per_split, split_stride);
-  else
-    DIB_LAUNCH((dib_wgrad_h1_kernel<CH, false, RELU>), grid, dim3(256), 0, st, dev_groups + c.first, dev_side, P, params, B, C,
-               bias_out, batch, c.count, tm, tn, nsplit, rows_per_split, split_stride);
+  WgradWaveGrid w;
+  if (int rc = wgrad_wave_grid(M, N, 128, c.count, nsplit, rows_per_split, &w)) return rc;
+  ProfScope ps(kProfWgradStream128, st, kPartWgradH1);   // timed with the kernel it stands in for
+  const auto kernel = w.ntl ? dib_wgrad_h1_kernel<CH, true, RELU> : dib_wgrad_h1_kernel<CH, false, RELU>;
+  DIB_LAUNCH(kernel, w.grid, dim3(256), 0, st, dev_groups + c.first, dev_side, P, params, B, C, bias_out, batch, c.count, w.tm, w.tn,
+             nsplit, rows_per_split, split_stride);
   return (int)hipGetLastError();
 }
 static int launch_wgrad_h1(int ch, bool relu, const DibGemmGroup* dev_groups, const DibWgradH1Side* dev_side, const GemmCall& c,
@@ -277,9 +280,8 @@ int launch_gemm(const DibGemmGroup* dev_groups, const GemmCall& c, const float* 
   if constexpr (MODE != 2) {
     // one large group in whole 128 x 128 x 32 tiles: global memory -> registers -> matrix cores (dib_gemm_stream.h; bit-identical
     // outputs).  host_groups: this call's group as the host sees it.
-    GemmStreamPlan gp;
-    if (gemm_stream_plan(MODE, host_groups, c, A, B, C, bias, aux, batch, act, &gp))
-      return launch_gemm_stream<MODE>(gp, dev_groups + c.first, host_groups[0], A, B, C, bias, aux, batch, act, st);
+    const auto [went, rc] = try_gemm_stream<MODE>(dev_groups + c.first, host_groups, c, A, B, C, bias, aux, batch, act, st);
+    if (went) return rc;
   }
   if constexpr (MODE == 2) {
     // 128-wide row-major operands in whole K-tiles: global memory -> registers -> matrix cores, one 128 x 128 (128 x 64) tile per
@@ -397,10 +399,9 @@ int dib_gemm(int mode, int M, int N, int K, const float* A, int lda, const float
   if (mode != 2) {   // a large product in whole tiles: the LDS-free kernel (dib_gemm_stream.h), bit-identical outputs
     GemmCall c;
     c.first = 0; c.count = 1; c.max_m = M; c.max_n = N;
-    GemmStreamPlan gp;
-    if (gemm_stream_plan(mode, &g, c, A, B, C, bias, aux, 0, act, &gp))
-      return mode == 0 ? launch_gemm_stream<0>(gp, dg, g, A, B, C, bias, aux, 0, act, st)
-                       : launch_gemm_stream<1>(gp, dg, g, A, B, C, bias, aux, 0, act, st);
+    const auto [went, rc] = mode == 0 ? try_gemm_stream<0>(dg, &g, c, A, B, C, bias, aux, 0, act, st)
+                                      : try_gemm_stream<1>(dg, &g, c, A, B, C, bias, aux, 0, act, st);
+    if (went) return rc;
   }
   ProfScope ps(mode * 4 + 3, st);
   const dim3 g1(8 * cdiv(tm, 8) * tn, 1, 1);

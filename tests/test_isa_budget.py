@@ -7,48 +7,9 @@ loop-carried accumulators resident in AGPRs (a divergent `if` around the MFMAs m
 AGPRs and back on every query tile: 441 + 264 `v_accvgpr_*` per tile instead of the zero-initialisations only), register
 budgets that keep 2 waves per SIMD where the design assumes them, and the MFMA count of each tile body (= the algorithmic
 FLOPs; a changed count means the arithmetic changed).  The thresholds are the current values plus a little slack."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "distributed-information-bottleneck.github.io_amd", "csrc", "dib_api.hip")
-
-
-def _hipcc():
-    for c in (shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
-        if c and os.path.exists(c):
-            return c
-    return None
-
-
-@pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    hipcc = _hipcc()
-    if hipcc is None:
-        pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("isa") / "dib_api.s")
-    res = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", SRC, "-o", out],
-                         capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-2000:]
-    text = open(out).read()
-    info = {}
-    for m in re.finditer(r"^(_Z\w+):[^\n]*\n", text, re.M):
-        end = text.find(".Lfunc_end", m.end())
-        if end < 0:
-            continue
-        body, tail = text[m.end():end], text[end:end + 4000]
-        meta = {k: int(v) for k, v in re.findall(r"; (NumVgprs|NumAgprs|ScratchSize|Occupancy|LDSByteSize): (\d+)", tail)}
-        if "NumVgprs" not in meta:
-            continue
-        meta["mfma"] = len(re.findall(r"^\s*v_mfma", body, re.M))
-        meta["accvgpr_write"] = len(re.findall(r"v_accvgpr_write", body))
-        meta["accvgpr_read"] = len(re.findall(r"v_accvgpr_read", body))
-        info[m.group(1)] = meta
-    return info
+from _isa import kernels  # noqa: F401  (the fixture: tests/_isa.py's one cross-compile, parsed)
 
 
 def _one(kernels, *needles):

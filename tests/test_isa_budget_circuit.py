@@ -1,36 +1,13 @@
 """Resource audit of the Boolean-circuit kernels (csrc/dib_circuit.h) in the generated gfx950 code, no GPU needed: no scratch
 and full occupancy headroom (256-thread workgroups, small register footprints)."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "distributed-information-bottleneck.github.io_amd", "csrc", "dib_api.hip")
-
-
-@pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    hipcc = next((c for c in (shutil.which("hipcc"), "/opt/rocm/bin/hipcc") if c and os.path.exists(c)), None)
-    if hipcc is None:
-        pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("isa_circuit") / "dib_api.s")
-    res = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", SRC, "-o", out],
-                         capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-2000:]
-    text = open(out).read()
-    info = {}
-    for m in re.finditer(r"^(_Z\w*dib_circuit\w+):[^\n]*\n", text, re.M):
-        end = text.find(".Lfunc_end", m.end())
-        tail = text[end:end + 4000]
-        info[m.group(1)] = {k: int(v) for k, v in re.findall(r"; (NumVgprs|NumAgprs|ScratchSize|Occupancy): (\d+)", tail)}
-    return info
+from _isa import family, kernels  # noqa: F401  (the fixture: tests/_isa.py's one cross-compile, parsed)
 
 
 @pytest.mark.parametrize("name", ["dib_circuit_fwd_kernel", "dib_circuit_bwd_kernel", "dib_circuit_mi_kernel"])
 def test_circuit_kernels_use_no_scratch(kernels, name):
+    kernels = family(kernels, "dib_circuit")
     hits = [k for k in kernels if name in k]
     assert len(hits) == 1, (name, sorted(kernels))
     k = kernels[hits[0]]
