@@ -82,6 +82,7 @@ class HipEngine:
         self._ws_pinned = set()                     # batch sizes whose workspace a captured graph points into
         self._ws_gen: Dict[int, int] = {}           # batch -> number of forwards that (re)wrote its activations
         self._scratch: Optional[torch.Tensor] = None
+        self._eval_ws: Dict[int, torch.Tensor] = {}   # batch -> initialised workspace of the evaluation helpers (feature_information)
         self._fused_head: Dict[int, bool] = {}      # loss kind -> dib_output_head_fused_supported
         self._infonce_ws: Dict[int, torch.Tensor] = {}   # batch -> workspace of dib_infonce_fwd_bwd
         self.blocks = self._query_blocks()
@@ -598,6 +599,88 @@ class HipEngine:
         rows = mi_sandwich_rows(self.lib, self.device, self.to_device(enc_out), seed, step, feature)
         m = rows.mean(dim=1).cpu().numpy()
         return float(m[0]), float(m[1])
+
+    # Most rows of one deterministic encode of feature_information (whole evaluation batches; one batch when a batch is larger).
+    # The encode's scratch is a full step workspace of that many rows - 0.2 MB per row at F = 64 with [128, 128] encoders: 417 MB
+    # here, 1.6 GB at 8192 - and larger launches gain little: 8 x 1024 rows at F = 64 take 5.83 / 5.20 / 5.04 / 5.03 ms with 1024 /
+    # 2048 / 4096 / 8192 rows per encode (tools/feature_information_bench.py, profiles/feature_information_bench.json).
+    FEATURE_INFORMATION_ROWS = 2048
+
+    def _evaluation_workspace(self, batch: int) -> torch.Tensor:
+        """An initialised workspace of `batch` rows that belongs to the evaluation helpers alone (never a step workspace: see
+        scratch); the two most recent sizes are kept - the full chunk and the tail chunk of feature_information."""
+        ws = self._eval_ws.pop(batch, None)
+        if ws is None:
+            nbytes = int(self.lib.dib_workspace_bytes(self.layout, batch))
+            if nbytes <= 0:
+                raise _lib.DibError(f"dib_workspace_bytes({batch}) -> {nbytes}")
+            while len(self._eval_ws) >= 2:
+                self._eval_ws.pop(next(iter(self._eval_ws)))
+            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
+            check(self.lib.dib_workspace_init(self.layout, batch, _ptr(ws), self._stream()), "dib_workspace_init")
+        self._eval_ws[batch] = ws
+        return ws
+
+    def feature_information(self, x_dev: torch.Tensor, rows, n: int, nb: int, seed: int, step0: int = 0, want_rows: bool = False,
+                            *, want_encodings: bool = False):
+        """The sandwich bounds of EVERY feature on nb evaluation batches of n rows: batch b is rows[b n : (b + 1) n] of the
+        dataset matrix x_dev [N, sum d_f] (device, float32), its noise keyed (seed, step0 + b, position i, feature f) - what
+        encode_feature + mi_sandwich_bounds(enc, seed, step0 + b, f) give per (feature, batch).  Per chunk of whole batches:
+        one deterministic dib_encoder_bank_fwd into an evaluation workspace and one dib_mi_features_bounds on its ENC_OUT
+        (include/dib_mi_features.h); nothing is read back before the end.  A shape outside that kernel's envelope takes the
+        per-feature loop.  Returns float64 numpy [F, nb, 2] (lower, upper) in nats; with want_rows also the per-row lower and
+        upper bounds [F, nb, n] each; with want_encodings also the encodings used, float32 [F, nb n, 2E]."""
+        F, E, n, nb = self.F, self.E, int(n), int(nb)
+        rows = self.to_device(rows, dtype=torch.int32).reshape(-1)
+        if rows.numel() != nb * n or x_dev.dim() != 2 or x_dev.shape[1] != self.sum_d:
+            raise ValueError(f"feature_information: {rows.numel()} rows for {nb} batches of {n}, inputs {tuple(x_dev.shape)}")
+        seed, step0 = int(seed) & (2 ** 64 - 1), int(step0)
+        dev, f64 = self.device, torch.float64
+        out = torch.empty((F, nb, 2), dtype=f64, device=dev)
+        lo = torch.empty((F, nb, n), dtype=f64, device=dev) if want_rows else None
+        up = torch.empty((F, nb, n), dtype=f64, device=dev) if want_rows else None
+        encs = torch.empty((F, nb * n, 2 * E), dtype=torch.float32, device=dev) if want_encodings else None
+        if not int(self.lib.dib_mi_features_supported(F, E, n, 1)):
+            col = np.concatenate([[0], np.cumsum(self.dims)])
+            for b in range(nb):
+                xb = x_dev[rows[b * n: (b + 1) * n].long()]
+                for f in range(F):
+                    enc = self.encode_feature(f, xb[:, col[f]: col[f + 1]])
+                    r = mi_sandwich_rows(self.lib, dev, enc, seed, step0 + b, f)
+                    out[f, b] = r.mean(dim=1)
+                    if want_rows:
+                        lo[f, b], up[f, b] = r[0], r[1]
+                    if want_encodings:
+                        encs[f, b * n: (b + 1) * n] = enc
+        else:
+            kb = max(1, min(nb, self.FEATURE_INFORMATION_ROWS // n, 65535 // F))
+            mi_ws = torch.empty(int(self.lib.dib_mi_features_workspace_bytes(F, E, n, kb)) // 8 + 2, dtype=f64, device=dev)
+            for b0 in range(0, nb, kb):
+                k = min(kb, nb - b0)
+                ws = self._evaluation_workspace(k * n)
+                check(self.lib.dib_encoder_bank_fwd(self.layout, _ptr(x_dev), x_dev.stride(0), _ptr(rows[b0 * n:]), 0, k * n,
+                                                    _ptr(self.params), 0, 0, _lib.FWD_DETERMINISTIC | _lib.FWD_INFERENCE,
+                                                    _ptr(ws), self._stream()), "dib_encoder_bank_fwd")
+                off = int(self.lib.dib_workspace_offset(self.layout, k * n, _lib.WS_ENC_OUT)) // 4
+                enc = ws[off: off + F * k * n * 2 * E]
+                part = out if k == nb else torch.empty((F, k, 2), dtype=f64, device=dev)
+                plo = lo if (k == nb or not want_rows) else torch.empty((F, k, n), dtype=f64, device=dev)
+                pup = up if (k == nb or not want_rows) else torch.empty((F, k, n), dtype=f64, device=dev)
+                check(self.lib.dib_mi_features_bounds(_ptr(enc), k * n, 0, F, E, n, k, seed, (step0 + b0) & 0xFFFFFFFF, 0,
+                                                      _ptr(part), _ptr(plo), _ptr(pup), None, _ptr(mi_ws), self._stream()),
+                      "dib_mi_features_bounds")
+                if k != nb:
+                    out[:, b0: b0 + k] = part
+                    if want_rows:
+                        lo[:, b0: b0 + k], up[:, b0: b0 + k] = plo, pup
+                if want_encodings:
+                    encs[:, b0 * n: (b0 + k) * n] = enc.view(F, k * n, 2 * E)
+        res = [out.cpu().numpy()]
+        if want_rows:
+            res += [lo.cpu().numpy(), up.cpu().numpy()]
+        if want_encodings:
+            res.append(encs.cpu().numpy())
+        return res[0] if len(res) == 1 else tuple(res)
 
     def eps(self, row_idx, row0: int, batch: int, seed: int, step: int) -> torch.Tensor:
         out = torch.empty((batch, self.F, self.E), dtype=torch.float32, device=self.device)

@@ -86,6 +86,8 @@ class History:
         self.history: Dict[str, List[float]] = {}
         self.epoch: List[int] = []
         self.model = None
+        # fit(track_information=...): {"epochs": [...], "beta": [...], "bounds": float64 [n_evals, F, 2] (lower, upper) nats}
+        self.information: Optional[dict] = None
 
 
 class Callback:
@@ -299,6 +301,29 @@ class DistributedIBNet:
             outs.append(eng.pred(b).clone())
         return torch.cat(outs, 0).cpu().numpy()
 
+    def information_per_feature(self, x, evaluation_batch_size=1024, number_evaluation_batches=8, seed=0, per_batch=False):
+        """Lower (InfoNCE) and upper (leave-one-out) bounds, in nats, on the information every feature's channel transmits
+        (reference utils.py:10-73 for each encoder, models.py:188-223): float64 [F, 2], the mean over the evaluation batches, or
+        [F, number_evaluation_batches, 2] with per_batch=True.
+
+        `x` is an input matrix [N, sum d_f] (array-like, or a float32 tensor already on the model's device).  The batches are the
+        rows utils.evaluation_batch_rows(N, evaluation_batch_size, number_evaluation_batches, seed) - the same rows for every
+        feature - and the noise of sample i of batch b of feature f is keyed (seed, b, i, f): the quantities
+        utils.estimate_mi_sandwich_bounds(self.feature_encoders[f], x_f, ..., seed=seed) gives feature by feature, here from
+        one encoder-bank forward and one dib_mi_features_bounds launch sequence per chunk of batches and ONE read-back
+        (engine.feature_information).  Nothing of the training state is touched.  Under torch.distributed every rank computes
+        the same numbers locally; there is no collective."""
+        from . import utils
+        eng = self._ensure_engine()
+        xd = x if isinstance(x, torch.Tensor) and x.device == eng.device and x.dtype == torch.float32 else eng.to_device(
+            x if isinstance(x, torch.Tensor) else np.asarray(x, dtype=np.float32))
+        if xd.dim() == 1:
+            xd = xd.view(-1, 1)
+        bs, nb = int(evaluation_batch_size), int(number_evaluation_batches)
+        rows = utils.evaluation_batch_rows(xd.shape[0], bs, nb, seed)
+        bounds = eng.feature_information(xd, rows.astype(np.int32), bs, nb, seed, 0)
+        return bounds if per_batch else bounds.mean(axis=1)
+
     # ---- compile / fit ---------------------------------------------------------------------
     def compile(self, optimizer='adam', loss=None, metrics=None, **_):
         """reference train.py:138-142."""
@@ -343,13 +368,19 @@ class DistributedIBNet:
         return logs
 
     def fit(self, x=None, y=None, batch_size=None, epochs=1, verbose=1, callbacks=None, validation_data=None,
-            shuffle=True, initial_epoch=0, **_):
+            shuffle=True, initial_epoch=0, track_information=None, **_):
         """reference train.py:157-166 `model.fit(x, y, epochs=, shuffle=True, batch_size=, callbacks=,
         verbose=, validation_data=)` -> History.
 
         Data parallel: when torch.distributed is initialised every rank calls fit() with the same
         arguments; each global batch is split row-wise across ranks, flat gradients are
         all-reduced (RCCL over xGMI with the nccl backend) and every rank applies the same update.
+
+        track_information: a dict - `x` (inputs to evaluate on; default: the validation inputs), `every` (epochs, default 1),
+        `evaluation_batch_size` (1024), `number_evaluation_batches` (8).  At the end of every epoch with epoch % every == 0
+        information_per_feature(x, ..., seed=epoch) is recorded in History.information = {"epochs", "beta", "bounds"
+        [n_evals, F, 2] nats} (not in History.history, whose lists stay one entry per epoch).  The inputs are uploaded once;
+        the evaluation reads the parameters and writes nothing the steps use: a tracked fit trains exactly like an untracked one.
         """
         if self.optimizer is None or self.loss is None:
             raise RuntimeError("call compile(optimizer=..., loss=...) before fit()")
@@ -374,12 +405,30 @@ class DistributedIBNet:
             if yv_np.ndim == 1:
                 yv_np = yv_np[:, None]
             xvd, yvd = eng.to_device(xv_np), eng.to_device(yv_np)
+        track = None
+        if track_information is not None:
+            track = dict(track_information)
+            unknown = set(track) - {"x", "every", "evaluation_batch_size", "number_evaluation_batches"}
+            if unknown:
+                raise ValueError(f"track_information: unknown keys {sorted(unknown)}")
+            if track.get("x") is not None:
+                xt = np.asarray(track["x"], dtype=np.float32)
+                track["x"] = eng.to_device(xt[:, None] if xt.ndim == 1 else xt)
+            elif validation_data is not None:
+                track["x"] = xvd
+            else:
+                raise ValueError("track_information needs inputs: give it `x` or fit(validation_data=...)")
+            track["every"] = int(track.get("every", 1))
+            if track["every"] < 1:
+                raise ValueError("track_information['every'] must be a positive number of epochs")
         cbs = list(callbacks or [])
         for cb in cbs:
             cb.set_model(self) if hasattr(cb, "set_model") else setattr(cb, "model", self)
         hist = History()
         hist.model = self
         self.history = hist
+        if track is not None:
+            hist.information = {"epochs": [], "beta": [], "bounds": np.zeros((0, F, 2))}
         self.stop_training = False
         kind = self.loss.kind
         for cb in cbs:
@@ -544,6 +593,13 @@ class DistributedIBNet:
                 for k, v in logs.items():
                     hist.history.setdefault(k, []).append(float(v))
                 hist.epoch.append(epoch)
+                if track is not None and epoch % track["every"] == 0:
+                    bounds = self.information_per_feature(track["x"], track.get("evaluation_batch_size", 1024),
+                                                          track.get("number_evaluation_batches", 8), seed=epoch)
+                    info = hist.information
+                    info["epochs"].append(epoch)
+                    info["beta"].append(float(self.beta.value()))
+                    info["bounds"] = np.concatenate([info["bounds"], bounds[None]], 0)
                 if verbose and rank == 0:
                     kls = sum(logs[f"KL{f}"] for f in range(F))
                     print(f"Epoch {epoch + 1}/{epochs} - loss: {logs['loss']:.4f} - sumKL: {kls:.4f} nats - "
@@ -731,10 +787,16 @@ class InfoPerFeatureCallback(Callback):
     Every `save_frequency` epochs, for each feature: `utils.estimate_mi_sandwich_bounds` on that feature's columns of
     the validation inputs; appends `[infonce_lower, loo_upper]` to `self.bounds` (same flat order as the reference:
     feature-major within an evaluation).  `validation_x` is the validation input matrix [N, sum d_f] (the reference
-    passes a tf.data.Dataset of (x, y) and strips y, models.py:210)."""
+    passes a tf.data.Dataset of (x, y) and strips y, models.py:210).
 
-    def __init__(self, save_frequency, validation_x, info_bound_batch_size=1024, info_bound_number_batches=8):
+    one_launch=True evaluates all features together - `model.information_per_feature(validation_x, ..., seed=epoch)`, the same
+    rows and noise keys, one encoder-bank forward and one bound evaluation per chunk of batches instead of one encode, one
+    bound call and one read-back per (feature, batch) - and fills `bounds` / `epochs` in the same layout."""
+
+    def __init__(self, save_frequency, validation_x, info_bound_batch_size=1024, info_bound_number_batches=8, one_launch=False):
         super().__init__()
+        self.one_launch = bool(one_launch)
+        self._x_dev = None
         self.save_frequency = save_frequency
         self.validation_x = np.asarray(validation_x, dtype=np.float32)
         self.bounds = []
@@ -744,6 +806,14 @@ class InfoPerFeatureCallback(Callback):
 
     def on_epoch_end(self, epoch, logs=None):
         if (epoch % self.save_frequency) != 0:
+            return
+        if self.one_launch:
+            if self._x_dev is None:   # uploaded once
+                self._x_dev = self.model._ensure_engine().to_device(self.validation_x)
+            b = self.model.information_per_feature(self._x_dev, self.info_bound_batch_size, self.info_bound_number_batches,
+                                                   seed=epoch)
+            self.bounds.extend([float(lo), float(up)] for lo, up in b)
+            self.epochs.append(epoch)
             return
         from . import utils
         idx = np.cumsum(self.model.feature_dimensionalities)[:-1]

@@ -40,6 +40,9 @@ def get_args(argv=None):
     p.add_argument('--feature_embedding_dimension', type=int, default=32)
     p.add_argument('--optimizer', type=str, default='adam')
     p.add_argument('--save_compression_matrices_frequency', type=int, default=0)
+    p.add_argument('--info_bounds_frequency', type=int, default=0,
+                   help='every N epochs: InfoNCE / leave-one-out bounds of every feature on the validation inputs '
+                        '(info_bounds.npz + distributed_info_plane_mi.png in --artifact_outdir); 0 = off')
     p.add_argument('--feature_encoder_architecture', type=int, nargs='+', default=[128, 128])
     p.add_argument('--number_positional_encoding_frequencies', type=int, default=5)
     p.add_argument('--integration_network_architecture', type=int, nargs='+', default=[256, 256])
@@ -148,7 +151,8 @@ def main(argv=None):
             dataset_dict.get('x_valid_raw', dataset_dict['x_valid']), args.artifact_outdir))
     history = model.fit(dataset_dict['x_train'], dataset_dict['y_train'], epochs=number_epochs, shuffle=True,
                         batch_size=args.batch_size, callbacks=callbacks, verbose=args.verbose,
-                        validation_data=(dataset_dict['x_valid'], dataset_dict['y_valid']))
+                        validation_data=(dataset_dict['x_valid'], dataset_dict['y_valid']),
+                        track_information=dict(every=args.info_bounds_frequency) if args.info_bounds_frequency > 0 else None)
     series = postprocess_history(history.history, dataset_dict['number_features'], dataset_dict['loss_is_info_based'])
     beta_series, kl_series, loss_series = series['beta'], series['kl_bits'], series['loss']
     kl_series_validation, loss_series_validation = series['kl_bits_validation'], series['loss_validation']
@@ -157,6 +161,11 @@ def main(argv=None):
         np.savez(os.path.join(args.artifact_outdir, 'history.npz'), beta=beta_series, kl_bits=kl_series,
                  loss=loss_series, kl_bits_validation=kl_series_validation, loss_validation=loss_series_validation)
         visualization.save_distributed_info_plane(kl_series_validation, loss_series_validation, args.artifact_outdir)
+        if history.information is not None:
+            info = history.information
+            np.savez(os.path.join(args.artifact_outdir, 'info_bounds.npz'), epochs=np.int64(info['epochs']),
+                     beta=np.float32(info['beta']), bounds=info['bounds'])
+            visualization.save_distributed_info_plane_mi(info, loss_series_validation, args.artifact_outdir)
     return history
 
 

@@ -50,6 +50,17 @@ def entropy_rate_scaling_ansatz(N, h_inf, gamma, c):
     return h_inf + np.log2(N) / (N ** gamma) / np.abs(c)
 
 
+def evaluation_batch_rows(n_rows, evaluation_batch_size, number_evaluation_batches, seed):
+    """The dataset rows of the evaluation batches of estimate_mi_sandwich_bounds: int64 [number_evaluation_batches,
+    evaluation_batch_size].  One np.random.default_rng(seed); per batch a shuffle without replacement (permutation(n)[:bs]),
+    or bs draws with replacement when the dataset has fewer rows than a batch.  Every feature of a model draws the same rows:
+    the rule takes nothing from the encoder."""
+    n, bs = int(n_rows), int(evaluation_batch_size)
+    rng = np.random.default_rng(seed)
+    return np.stack([rng.permutation(n)[:bs] if n >= bs else rng.integers(0, n, bs)
+                     for _ in range(int(number_evaluation_batches))]).astype(np.int64).reshape(-1, bs)
+
+
 def estimate_mi_sandwich_bounds(encoder, dataset, evaluation_batch_size=1024, number_evaluation_batches=8, seed=0):
     """Lower (InfoNCE) and upper (leave-one-out) bounds, in nats, on the information transmitted by one feature
     encoder (reference utils.py:10-73; Poole et al. 2019).
@@ -73,8 +84,7 @@ def estimate_mi_sandwich_bounds(encoder, dataset, evaluation_batch_size=1024, nu
     model = encoder._model
     eng = model._ensure_engine()
     estimates = []
-    for b in range(int(number_evaluation_batches)):
-        rows = rng.permutation(n)[:bs] if n >= bs else rng.integers(0, n, bs)
+    for b, rows in enumerate(evaluation_batch_rows(n, bs, number_evaluation_batches, seed)):
         enc_out = eng.encode_feature(encoder.index, x[rows])
         estimates.append(eng.mi_sandwich_bounds(enc_out, seed, b, encoder.index))
     return np.mean(np.stack(estimates, 0), 0)

@@ -120,3 +120,44 @@ def save_distributed_info_plane(kl_series, loss_series, outdir, entropy_y=None):
     fig.savefig(saveto, dpi=150)
     plt.close(fig)
     return saveto
+
+
+def save_distributed_info_plane_mi(information, loss_series, outdir, entropy_y=None):
+    """The distributed information plane in mutual-information bounds instead of KL: `information` is History.information of
+    DistributedIBNet.fit(track_information=...) - "bounds" [n_evals, F, 2] (InfoNCE lower, leave-one-out upper) in nats, "epochs"
+    [n_evals].  x: the summed mean-of-bounds (bits), with the band between the summed lower and upper bounds; y: the task loss
+    of those epochs (black; `loss_series` is either one value per epoch, indexed by "epochs", or one per evaluation); per-feature
+    mean-of-bounds on a twin axis.  A bound that is not finite (the upper bound of channels far apart) is drawn as its lower
+    bound.  Writes distributed_info_plane_mi.png next to save_distributed_info_plane's file."""
+    bounds = np.asarray(information["bounds"], dtype=np.float64) / np.log(2.0)
+    epochs = np.asarray(information["epochs"], dtype=np.int64)
+    if bounds.ndim != 3 or bounds.shape[2] != 2 or bounds.shape[0] != epochs.shape[0]:
+        raise ValueError(f"information['bounds'] {bounds.shape} must be [n_evals, F, 2] with one entry of 'epochs' each")
+    loss_series = np.asarray(loss_series, dtype=np.float64).reshape(-1)
+    perf = loss_series if loss_series.shape[0] == epochs.shape[0] else loss_series[epochs]
+    lower = bounds[..., 0]
+    upper = np.where(np.isfinite(bounds[..., 1]), bounds[..., 1], lower)
+    mid = 0.5 * (lower + upper)
+    number_features = bounds.shape[1]
+    full = np.sum(mid, axis=-1)
+    plt = _plt()
+    fig = plt.figure(figsize=(8, 4))
+    ax = fig.gca()
+    ax.fill_betweenx(perf, np.sum(lower, -1), np.sum(upper, -1), color='k', alpha=0.15, lw=0)
+    ax.plot(full, perf, lw=4, color='k')
+    hi = max(1.0, float(np.max(np.sum(upper, -1), initial=0.0)))
+    if entropy_y is not None:
+        ax.plot([0, hi], [entropy_y] * 2, 'k:')
+    ax.set_xlim([0, hi])
+    ax.set_xlabel('information about the features (bits)')
+    if number_features > 1:
+        ax2 = ax.twinx()
+        for f in range(number_features):
+            ax2.plot(full, mid[:, f], color=default_mpl_colors[f % len(default_mpl_colors)], lw=2)
+        ax.set_zorder(ax2.get_zorder() + 1)
+        ax.patch.set_visible(False)
+    os.makedirs(outdir, exist_ok=True)
+    saveto = os.path.join(outdir, 'distributed_info_plane_mi.png')
+    fig.savefig(saveto, dpi=150)
+    plt.close(fig)
+    return saveto

@@ -78,6 +78,10 @@ ORACLE_TESTS = {
                                 "test_ineligible_shapes_stay_on_the_tiled_kernel"},
     "test_gpu_input_grad.py": {"test_zoo_parity", "test_kernel_envelope", "test_grid_stride_rounds", "test_multi_tile_large_batch", "test_h1_not_stashed",
                                "test_addressing_and_guard_bands", "test_composition_upstream_module_gets_the_float64_gradient"},
+    "test_gpu_feature_information.py": {
+        "test_kernel_matches_oracle_across_the_envelope", "test_far_apart_gaussians_and_duplicated_rows",
+        "test_information_per_feature_matches_oracle_on_every_dispatch_path",
+        "test_validation_set_smaller_than_the_batch_draws_with_replacement"},
 }
 # tests that demand the bits (or fp32 summation-order tolerance) of a path the tests above check against an oracle
 EQUIVALENCE_TESTS = {
@@ -106,6 +110,12 @@ EQUIVALENCE_TESTS = {
     "test_gpu_mi_characterization.py": {
         "test_replay_split_calls_and_refusals", "test_bounds_from_parameters_reproduce_the_separation_zero_anchors",
         "test_characterize_on_a_small_sweep"},
+    "test_gpu_feature_information.py": {
+        "test_kernel_equals_the_sandwich_rows_loop", "test_replay_and_splits_are_bit_identical",
+        "test_chunks_of_batches_do_not_change_the_bits",
+        "test_all_features_equal_the_per_feature_loop_and_a_shape_beyond_the_envelope_takes_it",
+        "test_callback_in_one_launch_fills_bounds_like_information_per_feature",
+        "test_tracked_fit_trains_exactly_like_the_untracked_fit"},
 }
 
 
