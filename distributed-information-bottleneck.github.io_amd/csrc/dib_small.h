@@ -33,7 +33,6 @@ __host__ __device__ inline int dib_small_pick_nt(int n) {   // column tiles of 1
   if (n % 64 == 0 && (n / 64) % 4 == 0) return 4;
   if (n % 32 == 0 && (n / 32) % 4 == 0) return 2;
   if ((n / 16) % 4 == 0) return 1;
-  if (n % 64 == 0) return 4;
   if (n % 32 == 0) return 2;
   return 1;
 }
@@ -46,7 +45,6 @@ __host__ __device__ inline int dib_small_pick_nt_bwd(int kin) {
   if (tiles % 8 == 0) return 2;
   if (tiles % 4 == 0) return 1;
   if (tiles % 5 == 0) return 5;
-  if (tiles % 4 == 0) return 4;
   if (tiles % 2 == 0) return 2;
   return 1;
 }
@@ -559,8 +557,18 @@ __device__ __forceinline__ void dib_small_load_tile(const float* __restrict__ sr
   }
 }
 
-
 __host__ __device__ inline int dib_small_pitch(int width) { return (width + 63) / 64 * 64 + 4; }   // pitch % 64 == 4
+
+// ---- LDS maps -------------------------------------------------------------------------------------------------------------
+// The integration kernels (below) and the two chain kernels (dib_st_chain.h) each have one map next to them: the pitch and the place
+// of every region of the dynamic LDS, built from the shape by ONE function for both sides.  The kernel builds it over P = float*
+// from the start of its LDS and carves from it and from nothing else (the regions are then pointers, each the one before plus its
+// length); the host builds it over P = DibLdsFloats from 0 and sizes and admits the launch from `end` * sizeof(float) and from
+// nothing else.  A region added to a kernel is added to both.
+// (The two encoder kernels still carve by hand, against host/layout.h small_encoder_lds: the same carve through a map costs the
+// backward 7 VGPRs - 158 -> 165, same occupancy - for a reason not found, and the kernels' register counts are not to grow.)
+typedef long long DibLdsFloats;   // a float offset into the dynamic LDS / a launch's length in floats
+template <class P> __host__ __device__ __forceinline__ P dib_small_lds_take(P& o, int nfloats) { const P r = o; o += nfloats; return r; }
 
 // =====================================================================================================================
 // encoder bank forward
@@ -780,6 +788,41 @@ __device__ __forceinline__ void dib_small_cluster_slice(int width, int c, int cl
   col0 = 16 * t0; ncols = 16 * (t1 - t0);
 }
 
+// LDS map of the integration kernels.  wide_xch: the cluster kernels' exchange buffer; head: the launch has the 1-unit head's
+// scratch (without it the launch ends at the exchange buffer: the head's regions lie past `end` and nothing touches them).
+// n_hidden <= 3, and every loop over layers - here and in the kernel - is unrolled with a compile-time index, so that the pointer /
+// pitch arrays stay in registers.
+template <class P> struct DibSmallIntLds {
+  int pu, ph[3], po;        // pitches: input tile, hidden layers (0 from n_hidden up), pred / g_pred tile
+  P us, hs[3], gs[3], ps;   // u | h_0 .. h_{n-1} | dL/dh_0 .. dL/dh_{n-1} | pred / g_pred tile
+  P xch;                    // exchange buffer of the layer primitives
+  P red_w, red_l;           // head: [8][KL + 1] per-wave partials of d(w|b), [8][2] of {loss sum, #correct}   (KL = last hidden width)
+  P head_w, head_y;         // head: [KL] output-layer kernel then [1] bias, [16] labels of the tile's rows
+  P end;
+};
+template <class P>
+__host__ __device__ __forceinline__ DibSmallIntLds<P> dib_small_int_lds(P o, int K0, int n_hidden, const int* width /* [n_hidden] */,
+                                                                        int out_dim, bool wide_xch, bool head) {
+  DibSmallIntLds<P> m;
+  m.pu = dib_small_pitch(K0);
+  m.us = dib_small_lds_take(o, DIB_SMALL_ROWS * m.pu);
+#pragma unroll
+  for (int l = 0; l < 3; ++l) { m.ph[l] = l < n_hidden ? dib_small_pitch(width[l]) : 0; m.hs[l] = dib_small_lds_take(o, DIB_SMALL_ROWS * m.ph[l]); }
+#pragma unroll
+  for (int l = 0; l < 3; ++l) m.gs[l] = dib_small_lds_take(o, DIB_SMALL_ROWS * m.ph[l]);
+  m.po = dib_small_pitch(out_dim);
+  m.ps = dib_small_lds_take(o, DIB_SMALL_ROWS * m.po);
+  m.xch = dib_small_lds_take(o, wide_xch ? DIB_SMALL_XCH_FLOATS_WIDE : DIB_SMALL_XCH_FLOATS);
+  const P headless_end = o;
+  const int KL = n_hidden == 1 ? width[0] : (n_hidden == 2 ? width[1] : width[2]);
+  m.red_w = dib_small_lds_take(o, 8 * (KL + 1));
+  m.red_l = dib_small_lds_take(o, 16);
+  m.head_w = dib_small_lds_take(o, KL + 1);
+  m.head_y = dib_small_lds_take(o, DIB_SMALL_ROWS);
+  m.end = head ? o : headless_end;
+  return m;
+}
+
 // CLUSTER: workgroup `crank` of the a.cl that share `tile` (see above); else one workgroup per tile
 template <bool CLUSTER>
 __device__ __forceinline__ void dib_small_integration_body(const DibSmallIntArgs& a, const int tile, const int crank = 0) {
@@ -795,20 +838,14 @@ __device__ __forceinline__ void dib_small_integration_body(const DibSmallIntArgs
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r0 = tile * ROWS, rows_valid = min(ROWS, a.batch - r0);
   const int n = a.n_hidden;
-  // LDS map: u | h_0 .. h_{n-1} | g_0 .. g_{n-1} | pred / g_pred tile | head scratch.  (n <= 3; every loop over layers is
-  // unrolled with a compile-time index so that the pointer / pitch arrays stay in registers)
-  const int pu = dib_small_pitch(a.K0);
-  float* us = lds;
+  // (n <= 3; every loop over layers is unrolled with a compile-time index so that the pointer / pitch arrays stay in registers -
+  // as local copies: indexing the map's own arrays through references cost the cluster kernels 11 VGPRs and 144 B of scratch)
+  const DibSmallIntLds<float*> m = dib_small_int_lds<float*>(lds, a.K0, n, a.width, a.out_dim, CLUSTER, (a.mode & DIB_SMALL_INT_HEAD) != 0);
+  const int pu = m.pu, po = m.po;
+  float* us = m.us; float* ps = m.ps; float* xch = m.xch;
   float* hs[3]; float* gs[3]; int ph[3];
-  float* cur = us + ROWS * pu;
 #pragma unroll
-  for (int l = 0; l < 3; ++l) { ph[l] = l < n ? dib_small_pitch(a.width[l]) : 0; hs[l] = cur; cur += ROWS * ph[l]; }
-#pragma unroll
-  for (int l = 0; l < 3; ++l) { gs[l] = cur; cur += ROWS * ph[l]; }
-  const int po = dib_small_pitch(a.out_dim);
-  float* ps = cur; cur += ROWS * po;
-  float* xch = cur; cur += CLUSTER ? DIB_SMALL_XCH_FLOATS_WIDE : DIB_SMALL_XCH_FLOATS;
-  float* scratch = cur;   // head: [8][K + 1] + 16
+  for (int l = 0; l < 3; ++l) { ph[l] = m.ph[l]; hs[l] = m.hs[l]; gs[l] = m.gs[l]; }
   const bool stash = !(a.mode & DIB_SMALL_INT_INFER);
   const float slope = dib_neg_slope(a.act);
   // the last hidden layer (n is block-uniform: scalar selects)
@@ -823,8 +860,8 @@ __device__ __forceinline__ void dib_small_integration_body(const DibSmallIntArgs
   DIB_ST(16);
   // the head's own inputs - output weights, bias, the rows' labels - are fetched NOW into LDS: their global round trips (two
   // dependent ones for a gathered label) run under the hidden layers instead of in front of every row's loss
-  float* const head_w = scratch + 8 * (KL + 1) + 16;   // [KL] output-layer kernel, then [1] bias
-  float* const head_y = head_w + KL + 1;               // [16] labels of the tile's rows
+  float* const head_w = m.head_w;
+  float* const head_y = m.head_y;
   if (a.mode & DIB_SMALL_INT_HEAD) {
     for (int k = tid; k <= KL; k += DIB_SMALL_THREADS) head_w[k] = k < KL ? a.params[wo_off + k] : a.params[bo_off];
     if (tid < ROWS && tid < rows_valid) {
@@ -914,8 +951,8 @@ __device__ __forceinline__ void dib_small_integration_body(const DibSmallIntArgs
     const bool grad = (a.mode & DIB_SMALL_INT_HEAD_GRAD) != 0;
     const float* wv = head_w;            // LDS copies (written before the hidden layers, whose barriers publish them)
     const float b0 = head_w[KL];
-    float* redw = scratch;               // [8][KL + 1]
-    float* redl = scratch + 8 * (KL + 1); // [8][2]
+    float* redw = m.red_w;               // [8][KL + 1]
+    float* redl = m.red_l;               // [8][2]
     float lsum = 0.f, correct = 0.f, pb = 0.f;
     float pw[16];                        // KL <= 1024: 16 lane-strided columns
 #pragma unroll

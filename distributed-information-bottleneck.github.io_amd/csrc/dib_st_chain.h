@@ -41,6 +41,55 @@ struct DibStChainBwdArgs {
   unsigned* sync;        // one zero-initialised word (self-cleaning)
 };
 
+// LDS maps of the two kernels (dib_small.h "LDS maps": the kernel carves from it over float*, the host sizes and admits the launch
+// from it over DibLdsFloats).
+// Loops over the feed-forward layers are unrolled with a compile-time index: the pointer / pitch arrays stay in registers.
+template <class P> struct DibStChainFwdLds {
+  int pC, pD, pf[DIB_ST_CHAIN_MAX_FF];           // pitches of the HK-, D- and ff_width-wide tiles (0 from n_ff up)
+  P ctx, mha, h, f[DIB_ST_CHAIN_MAX_FF], xch;    // ctx tile | mha | h | ff_0 .. | exchange
+  P end;
+};
+template <class P> __host__ __device__ __forceinline__ DibStChainFwdLds<P> dib_st_chain_fwd_lds(P o, const DibStChainDesc& d) {
+  DibStChainFwdLds<P> m;
+  m.pC = dib_small_pitch(d.HK); m.pD = dib_small_pitch(d.D);
+  m.ctx = dib_small_lds_take(o, DIB_SMALL_ROWS * m.pC);
+  m.mha = dib_small_lds_take(o, DIB_SMALL_ROWS * m.pD);
+  m.h = dib_small_lds_take(o, DIB_SMALL_ROWS * m.pD);
+#pragma unroll
+  for (int l = 0; l < DIB_ST_CHAIN_MAX_FF; ++l) {
+    m.pf[l] = l < d.n_ff ? dib_small_pitch(d.ff_width[l]) : 0;
+    m.f[l] = dib_small_lds_take(o, DIB_SMALL_ROWS * m.pf[l]);
+  }
+  m.xch = dib_small_lds_take(o, DIB_SMALL_XCH_FLOATS);
+  m.end = o;
+  return m;
+}
+template <class P> struct DibStChainBwdLds {
+  int pD, pf[DIB_ST_CHAIN_MAX_FF];
+  P g, ga, gh, v;   // g (dL/dx') | g_a | g_h | v, [16][pD] each
+  P red;            // LayerNorm reduction scratch [2][16][D]
+  P gz[DIB_ST_CHAIN_MAX_FF], f[DIB_ST_CHAIN_MAX_FF];   // per ff layer: g_z tile, f tile
+  P xch, end;
+};
+template <class P> __host__ __device__ __forceinline__ DibStChainBwdLds<P> dib_st_chain_bwd_lds(P o, const DibStChainDesc& d) {
+  DibStChainBwdLds<P> m;
+  m.pD = dib_small_pitch(d.D);
+  m.g = dib_small_lds_take(o, DIB_SMALL_ROWS * m.pD);
+  m.ga = dib_small_lds_take(o, DIB_SMALL_ROWS * m.pD);
+  m.gh = dib_small_lds_take(o, DIB_SMALL_ROWS * m.pD);
+  m.v = dib_small_lds_take(o, DIB_SMALL_ROWS * m.pD);
+  m.red = dib_small_lds_take(o, 2 * DIB_SMALL_ROWS * d.D);
+#pragma unroll
+  for (int l = 0; l < DIB_ST_CHAIN_MAX_FF; ++l) {
+    m.pf[l] = l < d.n_ff ? dib_small_pitch(d.ff_width[l]) : 0;
+    m.gz[l] = dib_small_lds_take(o, DIB_SMALL_ROWS * m.pf[l]);
+    m.f[l] = dib_small_lds_take(o, DIB_SMALL_ROWS * m.pf[l]);
+  }
+  m.xch = dib_small_lds_take(o, DIB_SMALL_XCH_FLOATS);
+  m.end = o;
+  return m;
+}
+
 // y = LN(a + b) over the last axis for the tile's 16 rows: thread (row = tid >> 5, l = tid & 31) holds columns l + 32 c.
 // a: global [T][D] rows r0.. (rows >= rows_valid read as 0); b: LDS tile; y -> LDS tile (+ global), xhat / rstd -> global.
 // The expressions of dib_add_layernorm_fwd_kernel (two-pass variance, rstd = 1 / sqrt(var + eps)).
@@ -137,19 +186,12 @@ dib_st_chain_fwd_kernel(DibStChainFwdArgs a) {
   const int tile = blockIdx.x;
   const long long r0 = (long long)tile * DIB_SMALL_ROWS;
   const int rows_valid = (int)min((long long)DIB_SMALL_ROWS, a.T - r0);
-  const int D = d.D, pD = dib_small_pitch(D), pC = dib_small_pitch(d.HK);
-  // LDS: ctx tile | mha | h | ff_0 .. | exchange
-  float* cs = lds;
-  float* ms = cs + DIB_SMALL_ROWS * pC;
-  float* hs = ms + DIB_SMALL_ROWS * pD;
+  const DibStChainFwdLds<float*> m = dib_st_chain_fwd_lds<float*>(lds, d);
+  const int D = d.D, pD = m.pD, pC = m.pC;
+  float* cs = m.ctx; float* ms = m.mha; float* hs = m.h; float* xch = m.xch;
   float* fs[DIB_ST_CHAIN_MAX_FF]; int pf[DIB_ST_CHAIN_MAX_FF];
-  float* cur = hs + DIB_SMALL_ROWS * pD;
 #pragma unroll
-  for (int l = 0; l < DIB_ST_CHAIN_MAX_FF; ++l) {
-    pf[l] = l < d.n_ff ? dib_small_pitch(d.ff_width[l]) : 0;
-    fs[l] = cur; cur += DIB_SMALL_ROWS * pf[l];
-  }
-  float* xch = cur;
+  for (int l = 0; l < DIB_ST_CHAIN_MAX_FF; ++l) { pf[l] = m.pf[l]; fs[l] = m.f[l]; }
   const float slope = dib_neg_slope(d.act);
   dib_small_load_tile(a.ctx + r0 * d.HK, d.HK, d.HK, rows_valid, cs, pC);
   __syncthreads();
@@ -213,23 +255,13 @@ dib_st_chain_bwd_kernel(DibStChainBwdArgs a) {
   const int tile = blockIdx.x, tid = threadIdx.x;
   const long long r0 = (long long)tile * DIB_SMALL_ROWS;
   const int rows_valid = (int)min((long long)DIB_SMALL_ROWS, a.T - r0);
-  const int D = d.D, pD = dib_small_pitch(D);
+  const DibStChainBwdLds<float*> m = dib_st_chain_bwd_lds<float*>(lds, d);
+  const int D = d.D, pD = m.pD;
   const int nff = d.n_ff;
-  // LDS: g (dL/dx') | g_a | g_h | v | LN reduction scratch [2][16][D] | per ff layer: g_z tile, f tile | exchange
-  float* gs = lds;
-  float* ga = gs + DIB_SMALL_ROWS * pD;
-  float* gh = ga + DIB_SMALL_ROWS * pD;
-  float* vs = gh + DIB_SMALL_ROWS * pD;
-  float* red = vs + DIB_SMALL_ROWS * pD;
-  float* cur = red + 2 * DIB_SMALL_ROWS * D;
+  float* gs = m.g; float* ga = m.ga; float* gh = m.gh; float* vs = m.v; float* red = m.red; float* xch = m.xch;
   float* gz[DIB_ST_CHAIN_MAX_FF]; float* fs[DIB_ST_CHAIN_MAX_FF]; int pf[DIB_ST_CHAIN_MAX_FF];
 #pragma unroll
-  for (int l = 0; l < DIB_ST_CHAIN_MAX_FF; ++l) {
-    pf[l] = l < nff ? dib_small_pitch(d.ff_width[l]) : 0;
-    gz[l] = cur; cur += DIB_SMALL_ROWS * pf[l];
-    fs[l] = cur; cur += DIB_SMALL_ROWS * pf[l];
-  }
-  float* xch = cur;
+  for (int l = 0; l < DIB_ST_CHAIN_MAX_FF; ++l) { pf[l] = m.pf[l]; gz[l] = m.gz[l]; fs[l] = m.f[l]; }
   const float slope = dib_neg_slope(d.act);
   float* part = a.ln_partial + (long long)tile * 4 * D;
 
@@ -310,7 +342,7 @@ dib_st_chain_bwd_kernel(DibStChainBwdArgs a) {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   // 4 D columns x nch interleaved tile chunks (8 independent loads in flight per thread), chunks combined in order
   const int ncol = 4 * D, nch = max(1, DIB_SMALL_THREADS / ncol), ntl = (int)gridDim.x;
-  float* comb = lds;   // [nch][4 D]: every tile of this workgroup is done with its LDS
+  float* comb = gs;   // [nch][4 D] <= 1024 floats in the g tile's >= 16 x 68: every tile of this workgroup is done with its LDS
   for (int i0 = 0; i0 < ncol; i0 += DIB_SMALL_THREADS) {
     const int i = i0 + (tid % min(ncol, DIB_SMALL_THREADS)), ch = tid / min(ncol, DIB_SMALL_THREADS);
     if (i < ncol && ch < nch) {

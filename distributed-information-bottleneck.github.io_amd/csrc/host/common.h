@@ -14,6 +14,9 @@ constexpr int kMaxSplits = 32;   // partial slabs of a split-batch weight gradie
 constexpr int kSmallMaxBatch = 2048;     // rows
 constexpr int kSmallMaxEncWgs = 1024;    // row tiles x features (d(W1|b1) partials: one [16][H1] block per encoder workgroup)
 constexpr size_t kSmallMaxLds = 160 * 1024;   // LDS one workgroup of a row-tile kernel may have (gfx950: the CU's 160 KB)
+// dynamic LDS up to which a shape is ADMITTED to the integration and chain kernels: 10 KB below the CU's LDS, headroom for the
+// kernels' static __shared__ words and for regions a kernel gains later - an admitted shape must never become a refused launch
+constexpr size_t kSmallAdmitLds = 150 * 1024;
 constexpr int kSplitRows = 512;  // minimum batch rows per wgrad split: 8 K-tiles of 64 (measured: 2048 left mid-size batches with 16-256 workgroups)
 inline int64_t align_up(int64_t v, int64_t a = kAlign) { return (v + a - 1) / a * a; }
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

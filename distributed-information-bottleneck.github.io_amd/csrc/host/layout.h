@@ -152,6 +152,21 @@ static size_t small_encoder_lds(int H1, int H2, int E, bool bwd) {
   return (size_t)DIB_SMALL_ROWS * (20 + k * dib_small_pitch(H1) + k * dib_small_pitch(H2) + dib_small_pitch(2 * E)) * sizeof(float) +
          (size_t)DIB_SMALL_XCH_FLOATS_WIDE * sizeof(float);
 }
+// dynamic LDS bytes of the integration kernels, from the LDS map they carve from (dib_small.h "LDS maps"): hidden widths
+// width[n_hidden]; wide_xch: the cluster kernels; head: with the 1-unit head's scratch
+static size_t small_int_lds(int K0, int n_hidden, const int* width, int out_dim, bool wide_xch, bool head) {
+  return (size_t)dib_small_int_lds<DibLdsFloats>(0, K0, n_hidden, width, out_dim, wide_xch, head).end * sizeof(float);
+}
+// A network the row-tile integration kernel can run: 1-3 hidden layers of widths % 16 == 0 (<= 1024: the head's lane-strided dot)
+// and a piecewise-linear activation (dib_small.h dib_small_act).  small_int_lds against kSmallAdmitLds supplies the rest; the
+// input and output widths and the tuning knobs are each caller's own.
+static bool small_int_shape_ok(int n_hidden, const int* width, int act) {
+  if (n_hidden < 1 || n_hidden > 3) return false;
+  if (!(act >= 0 && act <= 2) && act != DIB_ACT_LEAKY_RELU_01) return false;
+  for (int i = 0; i < n_hidden; ++i)
+    if (width[i] < 16 || width[i] % 16 != 0 || width[i] > 1024) return false;
+  return true;
+}
 
 // ---- all weight gradients of a step in ONE grouped launch (host/gemm.h merged_wgrad) ----------------------------------------
 // Descriptors with absolute workspace offsets for this batch size (the activation buffers' offsets are not linear in the batch:
@@ -359,15 +374,12 @@ int dib_layout_create(int F, const int* feature_dims, int n_enc, const int* enc_
                 enc_units[0] <= 1024 && enc_units[1] <= 1024 && E <= 512 &&
                 small_encoder_lds(enc_units[0], enc_units[1], E, false) <= kSmallMaxLds &&
                 small_encoder_lds(enc_units[0], enc_units[1], E, true) <= kSmallMaxLds;
-    bool w_ok = n_int >= 1 && n_int <= 3 && (F * E) % 16 == 0;
-    int64_t fl = (int64_t)DIB_SMALL_ROWS * dib_small_pitch(F * E);
-    for (int i = 0; i < n_int && w_ok; ++i) {
-      w_ok = int_units[i] % 16 == 0 && int_units[i] <= 1024;
-      fl += 2ll * DIB_SMALL_ROWS * dib_small_pitch(int_units[i]);
+    // the layout's own: pl_act (the output activation too), an input of whole 16-unit tiles, and the launch size WITH the head's
+    // scratch whatever the output layer (one size serves the head and the general output layer)
+    if (pl_act && (F * E) % 16 == 0 && small_int_shape_ok(n_int, int_units, act)) {
+      l->sb_int_lds = (int)small_int_lds(F * E, n_int, int_units, out_dim, false, true);
+      l->sb_int = (size_t)l->sb_int_lds <= kSmallAdmitLds;
     }
-    fl += (int64_t)DIB_SMALL_ROWS * dib_small_pitch(out_dim) + DIB_SMALL_XCH_FLOATS + (w_ok ? 9 * (int_units[n_int - 1] + 1) + 32 : 0);
-    l->sb_int = pl_act && w_ok && fl * 4 <= 150 * 1024;
-    l->sb_int_lds = (int)(fl * 4);
   }
   *out = l;
   return DIB_OK;

@@ -24,24 +24,41 @@ static int small_cluster_size(const DibSmallIntArgs& a, size_t lds_bytes, int ot
   return weights >= knobs().int_cluster_min_weights ? cl : 1;
 }
 
+// the network part of an argument set: input width, hidden widths and (as width[n_hidden]) the output layer's, where the layers sit
+// in `params`, the activations
+static void small_fill_net(DibSmallIntArgs& a, const float* params, int K0, int n_hidden, const int* width, const int64_t* w_off,
+                           const int64_t* b_off, int act, int out_act) {
+  a.params = params; a.K0 = K0; a.n_hidden = n_hidden;
+  for (int i = 0; i <= n_hidden; ++i) { a.width[i] = width[i]; a.w_off[i] = w_off[i]; a.b_off[i] = b_off[i]; }
+  a.act = act; a.out_act = out_act; a.out_dim = width[n_hidden];
+}
+
+// arms cluster mode on an argument set - `cl` workgroups per row tile, arrival counters `sync` - and returns the x dimension of
+// its grid: 8 ceil(tiles / 8) x cl (dib_small.h dib_small_integration_cluster_kernel)
+static int small_arm_cluster(DibSmallIntArgs& a, int cl, unsigned* sync) {
+  a.cl = cl; a.cl_sync = sync; a.cl_agent_scope = knobs().int_cluster_short_exchange ? 0 : 1;
+  return 8 * cdiv(small_tiles(a.batch), 8) * cl;
+}
+
 // one launch of dib_small_integration_kernel; `mode` = DIB_SMALL_INT_* bits.  Head arguments may be null / 0 without a head.
 static int small_integration(dib_layout* l, const dib_layout::WsMap& m, float* w, int batch, const float* params, int mode,
                              int loss_kind, const float* y, int64_t ldy, const int32_t* row_idx, int64_t row0, float inv_bg,
                              hipStream_t st) {
   DibSmallIntArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.U = w + m.U; a.GU = w + m.g_u; a.batch = batch; a.K0 = l->F * l->E; a.params = params;
-  a.n_hidden = l->n_int;
-  for (int i = 0; i < l->n_int; ++i) { a.width[i] = l->int_units[i]; a.h[i] = w + m.int_h[i]; a.g[i] = w + m.g_int_h[i]; }
-  for (int i = 0; i <= l->n_int; ++i) { a.w_off[i] = l->int_w_off[i]; a.b_off[i] = l->int_b_off[i]; }
-  a.width[l->n_int] = l->out_dim;
-  a.act = l->act; a.out_act = l->out_act; a.out_dim = l->out_dim; a.mode = mode;
+  small_fill_net(a, params, l->F * l->E, l->n_int, l->int_width.data(), l->int_w_off.data(), l->int_b_off.data(), l->act, l->out_act);
+  a.U = w + m.U; a.GU = w + m.g_u; a.batch = batch; a.mode = mode;
+  // (xh: the exchange buffers of a cluster launch that writes no stashes; read in cluster mode only)
+  for (int i = 0; i < l->n_int; ++i) { a.h[i] = w + m.int_h[i]; a.g[i] = w + m.g_int_h[i]; a.xh[i] = w + m.cl_x[i]; }
   a.pred = w + m.pred; a.g_pred = w + m.g_pred;
   a.loss_kind = loss_kind; a.Y = y; a.ldy = ldy; a.row_idx = (const int*)row_idx; a.row0 = row0; a.inv_bg = inv_bg;
   a.partial_w = w + m.skinny_partial; a.partial_l = w + m.loss_partial;
-  // cluster mode: few row tiles, each on `cl` workgroups (dib_small.h)
-  const size_t cl_extra = (size_t)(DIB_SMALL_XCH_FLOATS_WIDE - DIB_SMALL_XCH_FLOATS) * sizeof(float);
-  int cl = small_cluster_size(a, (size_t)l->sb_int_lds + cl_extra);
+  // cluster mode: few row tiles, each on `cl` workgroups (dib_small.h); cl_extra: what the cluster kernels' wider exchange buffer adds
+  // to a launch (the two maps differ in that region alone, so it is the same for the companion)
+  const size_t lds = (size_t)l->sb_int_lds;
+  const size_t cl_extra = small_int_lds(a.K0, a.n_hidden, a.width, a.out_dim, true, true) - lds;
+  unsigned* const sync = (unsigned*)(w + m.cl_sync);
+  int cl = small_cluster_size(a, lds + cl_extra);
   if (t_companion.armed) {
     t_companion.armed = false;
     DibSmallIntPair p;
@@ -54,55 +71,42 @@ static int small_integration(dib_layout* l, const dib_layout::WsMap& m, float* w
     // its cluster, then this network sizes itself next to it
     if (small_tiles(batch) * cl + small_tiles(c.batch) * ccl > std::min(knobs().int_cluster_wgs, device_cus())) {
       ccl = 1;
-      cl = small_cluster_size(a, (size_t)l->sb_int_lds + cl_extra, small_tiles(c.batch));
+      cl = small_cluster_size(a, lds + cl_extra, small_tiles(c.batch));
     }
     // the cluster grid carries BOTH networks' tiles and the wide exchange buffer: each network fitting on its own is not enough
     // (a companion above 140 KB next to a clustered network) - then both run one workgroup per tile in the plain paired grid
-    if (std::max((size_t)l->sb_int_lds, t_companion.lds) + cl_extra > kSmallMaxLds) cl = ccl = 1;
-    if (cl > 1 || ccl > 1) {
-      p.s[0].cl = cl; p.s[0].cl_sync = (unsigned*)(w + m.cl_sync);
-      p.s[0].cl_agent_scope = c.cl_agent_scope = knobs().int_cluster_short_exchange ? 0 : 1;
-      for (int i = 0; i < l->n_int; ++i) p.s[0].xh[i] = w + m.cl_x[i];
-      c.cl = ccl; c.cl_sync = (unsigned*)(w + m.cl_sync) + (size_t)small_tiles(batch) * DIB_SMALL_CL_SYNC_WORDS;
-      const size_t lds = std::max((size_t)l->sb_int_lds, t_companion.lds) + cl_extra;
-      ProfScope ps(kProfOther, st);
-      const int gx = std::max(8 * cdiv(small_tiles(batch), 8) * cl, 8 * cdiv(small_tiles(c.batch), 8) * ccl);
-      return launch_lds<&dib_small_integration_pair_cluster_kernel>(dim3(gx, 2), dim3(DIB_SMALL_THREADS), lds, st, p);
+    const size_t both = std::max(lds, t_companion.lds);
+    if (both + cl_extra > kSmallMaxLds) cl = ccl = 1;
+    ProfScope ps(kProfOther, st);
+    if (cl > 1 || ccl > 1) {   // (the companion's arrival counters follow this network's)
+      const int gx = std::max(small_arm_cluster(p.s[0], cl, sync),
+                              small_arm_cluster(c, ccl, sync + (size_t)small_tiles(batch) * DIB_SMALL_CL_SYNC_WORDS));
+      return launch_lds<&dib_small_integration_pair_cluster_kernel>(dim3(gx, 2), dim3(DIB_SMALL_THREADS), both + cl_extra, st, p);
     }
-    const size_t lds = std::max((size_t)l->sb_int_lds, t_companion.lds);
-    ProfScope ps(kProfOther, st);
-    return launch_lds<&dib_small_integration_pair_kernel>(dim3(std::max(small_tiles(batch), small_tiles(p.s[1].batch)), 2),
-                                                          dim3(DIB_SMALL_THREADS), lds, st, p);
-  }
-  if (cl > 1) {
-    a.cl = cl; a.cl_sync = (unsigned*)(w + m.cl_sync); a.cl_agent_scope = knobs().int_cluster_short_exchange ? 0 : 1;
-    for (int i = 0; i < l->n_int; ++i) a.xh[i] = w + m.cl_x[i];
-    const size_t cl_lds = (size_t)l->sb_int_lds + cl_extra;
-    ProfScope ps(kProfOther, st);
-    return launch_lds<&dib_small_integration_cluster_kernel>(dim3(8 * cdiv(small_tiles(batch), 8) * cl), dim3(DIB_SMALL_THREADS), cl_lds,
-                                                             st, a);
+    return launch_lds<&dib_small_integration_pair_kernel>(dim3(std::max(small_tiles(batch), small_tiles(c.batch)), 2),
+                                                          dim3(DIB_SMALL_THREADS), both, st, p);
   }
   ProfScope ps(kProfOther, st);
-  return launch_lds<&dib_small_integration_kernel>(dim3(small_tiles(batch)), dim3(DIB_SMALL_THREADS), (size_t)l->sb_int_lds, st, a);
+  if (cl > 1) {
+    const int gx = small_arm_cluster(a, cl, sync);
+    return launch_lds<&dib_small_integration_cluster_kernel>(dim3(gx), dim3(DIB_SMALL_THREADS), lds + cl_extra, st, a);
+  }
+  return launch_lds<&dib_small_integration_kernel>(dim3(small_tiles(batch)), dim3(DIB_SMALL_THREADS), lds, st, a);
 }
 
 // ---- plain MLP on the row-tile kernels (include/dib_hip.h dib_mlp_small_*): dib_small_integration_kernel with its input
 // tile built from the batch's rows of X (DIB_SMALL_INT_POSENC_IN) and the dgrad chain stopped at the first layer ----
-static int64_t mlp_small_lds_floats(const dib_mlp_desc* d) {
-  const int nf = d->n_freq > 1 ? d->n_freq : 1;
-  int64_t fl = (int64_t)DIB_SMALL_ROWS * dib_small_pitch(d->in_dim * nf);
-  for (int i = 0; i < d->n_hidden; ++i) fl += 2ll * DIB_SMALL_ROWS * dib_small_pitch(d->width[i]);
-  return fl + (int64_t)DIB_SMALL_ROWS * dib_small_pitch(d->width[d->n_hidden]) + DIB_SMALL_XCH_FLOATS;
+static int mlp_n_freq(const dib_mlp_desc* d) { return d->n_freq > 1 ? d->n_freq : 1; }
+// dynamic LDS bytes of the single-workgroup kernel for this MLP; head: with the 1-unit head's scratch (dib_mlp_small_head_step)
+static size_t mlp_small_lds(const dib_mlp_desc* d, bool head) {
+  return small_int_lds(d->in_dim * mlp_n_freq(d), d->n_hidden, d->width, d->width[d->n_hidden], false, head);
 }
 static void mlp_small_fill(const dib_mlp_desc* d, DibSmallIntArgs& a, const float* params, int n) {
-  const int nf = d->n_freq > 1 ? d->n_freq : 1;
-  a.batch = n; a.K0 = d->in_dim * nf; a.params = params; a.n_hidden = d->n_hidden;
-  for (int i = 0; i <= d->n_hidden; ++i) { a.width[i] = d->width[i]; a.w_off[i] = d->w_off[i]; a.b_off[i] = d->b_off[i]; }
-  a.act = d->act; a.out_act = 0; a.out_dim = d->width[d->n_hidden];
-  a.in_dim = d->in_dim; a.n_freq = nf;
+  small_fill_net(a, params, d->in_dim * mlp_n_freq(d), d->n_hidden, d->width, d->w_off, d->b_off, d->act, 0);
+  a.batch = n; a.in_dim = d->in_dim; a.n_freq = mlp_n_freq(d);
 }
 static int mlp_small_launch(const dib_mlp_desc* d, const DibSmallIntArgs& a, hipStream_t st) {
-  const size_t lds = (size_t)mlp_small_lds_floats(d) * 4;
+  const size_t lds = mlp_small_lds(d, false);
   ProfScope ps(kProfOther, st);
   return launch_lds<&dib_small_integration_kernel>(dim3(small_tiles(a.batch)), dim3(DIB_SMALL_THREADS), lds, st, a);
 }
@@ -135,17 +139,10 @@ static int mlp_small_bwd_args(const dib_mlp_desc* d, const float* params, const 
   mlp_small_fill(d, a, params, n);
   return DIB_OK;
 }
-// ---- plain MLP with a 1-unit head: the whole training step of the head network in ONE launch (include/dib_hip.h) ----
-static int64_t mlp_head_lds_floats(const dib_mlp_desc* d) {
-  int64_t fl = (int64_t)DIB_SMALL_ROWS * dib_small_pitch(d->in_dim);
-  for (int i = 0; i < d->n_hidden; ++i) fl += 2ll * DIB_SMALL_ROWS * dib_small_pitch(d->width[i]);
-  return fl + (int64_t)DIB_SMALL_ROWS * dib_small_pitch(1) + DIB_SMALL_XCH_FLOATS + 9 * (d->width[d->n_hidden - 1] + 1) + 32;
-}
-
 // the companion protocol: arm, run the model's entry point, launch alone if the model's path had no row-tile launch to share
 static int with_companion(const dib_mlp_desc* d, const DibSmallIntArgs& c, hipStream_t st, int model_rc_fn(void*), void* ctx) {
   t_companion.args = c;
-  t_companion.lds = (size_t)mlp_small_lds_floats(d) * 4;
+  t_companion.lds = mlp_small_lds(d, false);
   t_companion.armed = true;
   int rc = model_rc_fn(ctx);
   if (t_companion.armed) {
@@ -159,13 +156,12 @@ extern "C" {
 
 int dib_mlp_small_supported(const dib_mlp_desc* d, int batch) {
   if (!d || !knobs().small_batch || !knobs().mlp_row_tiles || batch < 1 || batch > kSmallMaxBatch) return 0;
-  if (d->n_hidden < 1 || d->n_hidden > 3 || d->in_dim < 1) return 0;
-  if (!(d->act >= 0 && d->act <= 2) && d->act != DIB_ACT_LEAKY_RELU_01) return 0;   // piecewise-linear activations only
-  const int nf = d->n_freq > 1 ? d->n_freq : 1;
-  if ((int64_t)d->in_dim * nf > 1024) return 0;
-  for (int i = 0; i <= d->n_hidden; ++i)
-    if (d->width[i] < 16 || d->width[i] % 16 != 0 || d->width[i] > 1024) return 0;
-  return mlp_small_lds_floats(d) * 4 <= 150 * 1024 ? 1 : 0;
+  if (!small_int_shape_ok(d->n_hidden, d->width, d->act)) return 0;
+  // its own: any input of up to 1024 encoded columns; the output layer on row tiles too
+  if (d->in_dim < 1 || (int64_t)d->in_dim * mlp_n_freq(d) > 1024) return 0;
+  const int out = d->width[d->n_hidden];
+  if (out < 16 || out % 16 != 0 || out > 1024) return 0;
+  return mlp_small_lds(d, false) <= kSmallAdmitLds ? 1 : 0;
 }
 int dib_mlp_small_fwd(const dib_mlp_desc* d, const float* params, const float* x, int64_t ldx, const int32_t* row_idx, int n,
                       float* a0, float* const* h, float* out, dib_stream_t stream) {
@@ -183,12 +179,11 @@ int dib_mlp_small_bwd(const dib_mlp_desc* d, const float* params, const float* g
 }
 int dib_mlp_small_head_supported(const dib_mlp_desc* d, int n) {
   if (!d || !knobs().small_batch || !knobs().mlp_row_tiles || n < 1 || n > kSmallMaxBatch) return 0;
-  if (d->n_hidden < 1 || d->n_hidden > 3 || d->in_dim < 16 || d->in_dim % 16 || d->in_dim > 1024 || d->n_freq > 1) return 0;
-  if (!(d->act >= 0 && d->act <= 2) && d->act != DIB_ACT_LEAKY_RELU_01) return 0;
-  for (int i = 0; i < d->n_hidden; ++i)
-    if (d->width[i] < 16 || d->width[i] % 16 != 0 || d->width[i] > 1024) return 0;
+  if (!small_int_shape_ok(d->n_hidden, d->width, d->act)) return 0;
+  // its own: an input of whole 16-unit tiles (dL/dx), no positional encoding, the 1-unit output
+  if (d->in_dim < 16 || d->in_dim % 16 || d->in_dim > 1024 || d->n_freq > 1) return 0;
   if (d->width[d->n_hidden] != 1) return 0;
-  return mlp_head_lds_floats(d) * 4 <= 150 * 1024 ? 1 : 0;
+  return mlp_small_lds(d, true) <= kSmallAdmitLds ? 1 : 0;
 }
 int64_t dib_mlp_small_head_workspace_bytes(const dib_mlp_desc* d, int n) {
   if (!d || n < 1 || d->n_hidden < 1 || d->n_hidden > 3) return DIB_E_ARG;
@@ -204,13 +199,12 @@ int dib_mlp_small_head_step(const dib_mlp_desc* d, const float* params, const fl
   std::memset(&a, 0, sizeof(a));
   a.mode = DIB_SMALL_INT_FWD | DIB_SMALL_INT_HEAD | DIB_SMALL_INT_HEAD_GRAD | DIB_SMALL_INT_BWD | DIB_SMALL_INT_HEAD_REDUCE |
            (g_x ? 0 : DIB_SMALL_INT_NO_GU);
-  a.U = x; a.GU = g_x; a.batch = n; a.K0 = d->in_dim; a.params = params; a.n_hidden = d->n_hidden;
-  for (int i = 0; i <= d->n_hidden; ++i) { a.width[i] = d->width[i]; a.w_off[i] = d->w_off[i]; a.b_off[i] = d->b_off[i]; }
+  small_fill_net(a, params, d->in_dim, d->n_hidden, d->width, d->w_off, d->b_off, d->act, 0);   // (the 1-unit output: out_dim = 1)
+  a.U = x; a.GU = g_x; a.batch = n;
   for (int i = 0; i < d->n_hidden; ++i) {
     if (!h[i] || !g[i]) return DIB_E_ARG;
     a.h[i] = h[i]; a.g[i] = g[i];
   }
-  a.act = d->act; a.out_act = 0; a.out_dim = 1;
   a.pred = pred; a.g_pred = g_pred; a.loss_kind = loss_kind; a.Y = y; a.ldy = ldy; a.row_idx = nullptr; a.row0 = 0;
   a.inv_bg = inv_global_batch;
   const int tiles = small_tiles(n), KL = d->width[d->n_hidden - 1];
@@ -219,7 +213,7 @@ int dib_mlp_small_head_step(const dib_mlp_desc* d, const float* params, const fl
   a.sync = (unsigned*)(a.partial_l + 2 * tiles);   // zero at first use (the caller zero-fills the workspace once)
   a.head_gw = grads + d->w_off[d->n_hidden]; a.head_gb = grads + d->b_off[d->n_hidden];
   a.sums3 = sums3; a.loss_scale = inv_global_batch;
-  const size_t lds = (size_t)mlp_head_lds_floats(d) * 4;
+  const size_t lds = mlp_small_lds(d, true);
   ProfScope ps(kProfOther, (hipStream_t)stream);
   return launch_lds<&dib_small_integration_kernel>(dim3(tiles), dim3(DIB_SMALL_THREADS), lds, (hipStream_t)stream, a);
 }

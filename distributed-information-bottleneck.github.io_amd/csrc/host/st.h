@@ -5,16 +5,9 @@ static int ln_grid(int64_t T, int D) { return grid_for(T, D <= 32 ? 8 : 4, 512);
 
 // ---- the token-wise half of a set-transformer block in one launch per direction (csrc/dib_st_chain.h) ----------------
 static_assert(sizeof(dib_st_block_desc) == sizeof(DibStChainDesc), "public block descriptor must mirror the kernel's");
-static size_t st_chain_fwd_lds(const dib_st_block_desc* d) {
-  size_t fl = (size_t)DIB_SMALL_ROWS * (dib_small_pitch(d->HK) + 2 * dib_small_pitch(d->D)) + DIB_SMALL_XCH_FLOATS;
-  for (int l = 0; l < d->n_ff; ++l) fl += (size_t)DIB_SMALL_ROWS * dib_small_pitch(d->ff_width[l]);
-  return fl * sizeof(float);
-}
-static size_t st_chain_bwd_lds(const dib_st_block_desc* d) {
-  size_t fl = (size_t)DIB_SMALL_ROWS * (4 * dib_small_pitch(d->D) + 2 * d->D) + DIB_SMALL_XCH_FLOATS;
-  for (int l = 0; l < d->n_ff; ++l) fl += 2 * (size_t)DIB_SMALL_ROWS * dib_small_pitch(d->ff_width[l]);
-  return fl * sizeof(float);
-}
+// dynamic LDS bytes of the two kernels, from the LDS maps they carve from (dib_st_chain.h)
+static size_t st_chain_fwd_lds(const DibStChainDesc& d) { return (size_t)dib_st_chain_fwd_lds<DibLdsFloats>(0, d).end * sizeof(float); }
+static size_t st_chain_bwd_lds(const DibStChainDesc& d) { return (size_t)dib_st_chain_bwd_lds<DibLdsFloats>(0, d).end * sizeof(float); }
 
 extern "C" {
 
@@ -92,7 +85,9 @@ int dib_st_chain_supported(const dib_st_block_desc* d, int64_t T) {
     if (d->ff_width[l] <= 0 || d->ff_width[l] % 16 || d->ff_width[l] > 1024) return 0;
   if (d->ff_width[d->n_ff - 1] != d->D) return 0;
   if (T > 4096) return 0;   // above: one tiled GEMM per layer reads each weight once per 64-128 rows instead of once per 16
-  return st_chain_fwd_lds(d) <= 150 * 1024 && st_chain_bwd_lds(d) <= 150 * 1024;
+  DibStChainDesc k;
+  std::memcpy(&k, d, sizeof(k));
+  return st_chain_fwd_lds(k) <= kSmallAdmitLds && st_chain_bwd_lds(k) <= kSmallAdmitLds;
 }
 
 int64_t dib_st_chain_workspace_bytes(int64_t T, int D) {
@@ -110,7 +105,7 @@ int dib_st_chain_fwd(const dib_st_block_desc* d, int64_t T, const float* params,
   a.T = T; a.params = params; a.ctx = ctx; a.x_in = x_in; a.h = h; a.xhat1 = xhat1; a.rstd1 = rstd1;
   for (int l = 0; l < d->n_ff; ++l) { if (!ff[l]) return DIB_E_ARG; a.ff[l] = ff[l]; }
   a.x_out = x_out; a.xhat2 = xhat2; a.rstd2 = rstd2;
-  const size_t lds = st_chain_fwd_lds(d);
+  const size_t lds = st_chain_fwd_lds(a.d);
   return launch_lds<&dib_st_chain_fwd_kernel>(dim3((unsigned)((T + DIB_SMALL_ROWS - 1) / DIB_SMALL_ROWS)), dim3(DIB_SMALL_THREADS), lds,
                                               (hipStream_t)stream, a);
 }
@@ -132,7 +127,7 @@ int dib_st_chain_bwd(const dib_st_block_desc* d, int64_t T, const float* params,
   const long long tiles = (T + DIB_SMALL_ROWS - 1) / DIB_SMALL_ROWS;
   a.ln_partial = (float*)ws;
   a.sync = (unsigned*)((float*)ws + tiles * 4 * d->D);   // zero at first use (the caller zero-fills the workspace once)
-  const size_t lds = st_chain_bwd_lds(d);
+  const size_t lds = st_chain_bwd_lds(a.d);
   return launch_lds<&dib_st_chain_bwd_kernel>(dim3((unsigned)tiles), dim3(DIB_SMALL_THREADS), lds, (hipStream_t)stream, a);
 }
 

@@ -37,7 +37,7 @@ from _oracle_pred_grad import backward_from_pred_grad
 # ---- the kernels' width-dependent selections (csrc/dib_small.h), restated ONLY to check that the case table reaches each ----
 
 
-def _pick_nt(n):   # dib_small_pick_nt -> which return statement (the fourth, n % 64 == 0 after (n / 16) % 4 != 0, is unreachable)
+def _pick_nt(n):   # dib_small_pick_nt -> which return statement
     t = n // 16
     if n % 64 == 0 and (n // 64) % 4 == 0:
         return "nt4:T%16"
@@ -50,7 +50,7 @@ def _pick_nt(n):   # dib_small_pick_nt -> which return statement (the fourth, n 
     return "nt1:odd"
 
 
-def _pick_nt_bwd(kin):   # dib_small_pick_nt_bwd (the sixth return, tiles % 4 after tiles % 4, is unreachable)
+def _pick_nt_bwd(kin):   # dib_small_pick_nt_bwd -> which return statement
     t = kin // 16
     for m, name in ((20, "nt5:T%20"), (16, "nt4:T%16"), (8, "nt2:T%8"), (4, "nt1:T%4"), (5, "nt5:T%5"), (2, "nt2:T%2")):
         if t % m == 0:
