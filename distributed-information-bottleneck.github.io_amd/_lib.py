@@ -268,6 +268,13 @@ SIGNATURES_MI_FEATURES = {
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
+# include/dib_compression.h: the compression-scheme matrices of every feature of a DistributedIBNet in one evaluation
+SIGNATURES_COMPRESSION = {
+    "dib_compression_supported": (c_int, [c_int, c_int, c_int]),
+    "dib_compression_gather": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
+    "dib_compression_matrices": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+}
+
 
 def load_library(build_if_missing: bool = True):
     """dlopen libdib_hip.so and attach signatures.  Raises (no fallback) if it cannot be loaded."""
@@ -304,7 +311,8 @@ def _attach(lib):
         raise RuntimeError(f"libdib_hip ABI version {have} != {ABI_VERSION} expected by this binding ({getattr(lib, '_name', '?')}): "
                            "rebuild it (python -c 'import __graft_entry__ as g; g.build()' / tools/build_variant.sh)")
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_ST.items()) + list(SIGNATURES_MEASURE.items()) \
-            + list(SIGNATURES_CIRCUIT.items()) + list(SIGNATURES_PARTITION.items()) + list(SIGNATURES_MI_CHANNEL.items()) + list(SIGNATURES_MI_FEATURES.items()):
+            + list(SIGNATURES_CIRCUIT.items()) + list(SIGNATURES_PARTITION.items()) + list(SIGNATURES_MI_CHANNEL.items()) + list(SIGNATURES_MI_FEATURES.items()) \
+            + list(SIGNATURES_COMPRESSION.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

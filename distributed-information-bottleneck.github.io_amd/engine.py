@@ -682,6 +682,67 @@ class HipEngine:
             res.append(encs.cpu().numpy())
         return res[0] if len(res) == 1 else tuple(res)
 
+    def compression_matrices(self, x_dev: torch.Tensor, rows, counts, want_distances: bool = False, *, want_encodings: bool = False):
+        """The compression-scheme matrix exp(-Bhattacharyya distance) of EVERY feature on its own display rows: feature f is
+        shown on rows[f, :counts[f]] of the dataset matrix x_dev [N, sum d_f] (device, float32); rows is an int32 host table
+        [F, n_max] (entries beyond counts[f] are padding, any valid row).  One dib_compression_gather, one deterministic
+        dib_encoder_bank_fwd of n_max rows into an evaluation workspace, one dib_compression_matrices on its ENC_OUT
+        (include/dib_compression.h) and ONE read-back.  A shape outside that kernel's envelope takes the per-feature launches
+        (encode_feature + bhattacharyya).  Returns float32 numpy [F, n_max, n_max], zero outside [:counts[f], :counts[f]]; with
+        want_distances also the distances in the same layout; with want_encodings also the encodings used, float32
+        [F, n_max, 2E] (rows beyond counts[f] are the padding's).  A row index outside [0, N) raises ValueError before any launch.
+        Nothing of the training state is touched."""
+        F, E = self.F, self.E
+        rows = np.ascontiguousarray(rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows))
+        counts = np.asarray(counts.detach().cpu().numpy() if isinstance(counts, torch.Tensor) else counts).reshape(-1)
+        if x_dev.dim() != 2 or x_dev.shape[1] != self.sum_d or rows.ndim != 2 or rows.shape[0] != F or rows.shape[1] < 1 \
+                or counts.shape[0] != F:
+            raise ValueError(f"compression_matrices: rows {rows.shape}, counts {counts.shape} for {F} features, inputs "
+                             f"{tuple(x_dev.shape)}")
+        n_max, N = int(rows.shape[1]), int(x_dev.shape[0])
+        if not (np.issubdtype(rows.dtype, np.integer) and np.issubdtype(counts.dtype, np.integer)):
+            raise ValueError("compression_matrices: rows and counts must be integer tables")
+        if rows.min() < 0 or rows.max() >= N or counts.min() < 0 or counts.max() > n_max:
+            raise ValueError(f"compression_matrices: row indices must lie in [0, {N}) and counts in [0, {n_max}]")
+        dev = self.device
+        if not int(self.lib.dib_compression_supported(F, E, n_max)):
+            col = np.concatenate([[0], np.cumsum(self.dims)])
+            comp = np.zeros((F, n_max, n_max), dtype=np.float32)
+            dist = np.zeros((F, n_max, n_max), dtype=np.float32) if want_distances else None
+            encs = np.zeros((F, n_max, 2 * E), dtype=np.float32) if want_encodings else None
+            for f in range(F):
+                c = int(counts[f])
+                if c == 0:
+                    continue
+                idx = torch.from_numpy(rows[f, :c].astype(np.int64)).to(dev)
+                enc = self.encode_feature(f, x_dev[idx][:, col[f]: col[f + 1]])
+                if want_encodings:
+                    encs[f, :c] = enc.cpu().numpy()
+                mu, lv = enc[:, :E], enc[:, E:]
+                d = self.bhattacharyya(mu, lv, mu, lv).cpu().numpy()
+                comp[f, :c, :c] = np.exp(-d)
+                if want_distances:
+                    dist[f, :c, :c] = d
+            res = [comp] + ([dist] if want_distances else []) + ([encs] if want_encodings else [])
+            return res[0] if len(res) == 1 else tuple(res)
+        table = self.to_device(np.concatenate([rows.reshape(-1), counts]).astype(np.int32), dtype=torch.int32)   # one upload
+        xg = torch.empty((n_max, self.sum_d), dtype=torch.float32, device=dev)
+        check(self.lib.dib_compression_gather(self.layout, _ptr(x_dev), x_dev.stride(0), N, _ptr(table), n_max, _ptr(xg),
+                                              self._stream()), "dib_compression_gather")
+        ws = self._evaluation_workspace(n_max)
+        check(self.lib.dib_encoder_bank_fwd(self.layout, _ptr(xg), self.sum_d, None, 0, n_max, _ptr(self.params), 0, 0,
+                                            _lib.FWD_DETERMINISTIC | _lib.FWD_INFERENCE, _ptr(ws), self._stream()),
+              "dib_encoder_bank_fwd")
+        off = int(self.lib.dib_workspace_offset(self.layout, n_max, _lib.WS_ENC_OUT)) // 4
+        enc = ws[off: off + F * n_max * 2 * E]
+        out = torch.empty((2 if want_distances else 1, F, n_max, n_max), dtype=torch.float32, device=dev)
+        check(self.lib.dib_compression_matrices(_ptr(enc), n_max, 0, F, E, _ptr(table[F * n_max:]), n_max,
+                                                _ptr(out[1]) if want_distances else None, _ptr(out[0]), self._stream()),
+              "dib_compression_matrices")
+        host = out.cpu().numpy()
+        res = [host[0]] + ([host[1]] if want_distances else []) + ([enc.view(F, n_max, 2 * E).cpu().numpy()] if want_encodings else [])
+        return res[0] if len(res) == 1 else tuple(res)
+
     def eps(self, row_idx, row0: int, batch: int, seed: int, step: int) -> torch.Tensor:
         out = torch.empty((batch, self.F, self.E), dtype=torch.float32, device=self.device)
         check(self.lib.dib_philox_normal_fill(_ptr(out), _ptr(row_idx), int(row0), batch, self.F, self.E, int(seed),

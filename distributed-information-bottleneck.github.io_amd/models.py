@@ -324,6 +324,51 @@ class DistributedIBNet:
         bounds = eng.feature_information(xd, rows.astype(np.int32), bs, nb, seed, 0)
         return bounds if per_batch else bounds.mean(axis=1)
 
+    def compression_matrices(self, x_processed, x_raw=None, max_number_to_display=128, rng=None, return_distances=False,
+                             cache=None):
+        """The compression scheme of every feature (reference visualization.py:14-81, models.py:152-186): for feature f the
+        matrix exp(-Bhattacharyya distance) between the Gaussians its encoder assigns to a display sample of its values.
+        Returns a list of F dicts: "matrix" float32 [n_f, n_f], "indices" (the sample's rows of x_processed), "values" (their
+        raw values, sorted), "counts" (the value frequencies of a feature with < 10 unique values, else None) and, with
+        return_distances, "distances" [n_f, n_f].
+
+        `x_processed` is the input matrix [N, sum d_f] (array-like, or a float32 tensor already on the model's device), `x_raw`
+        the matrix of the same shape the sample is drawn and labelled from (default: x_processed).  The samples are
+        visualization.display_rows(x_raw, ..., rng, cache): the rows visualization.save_compression_matrices draws feature by
+        feature under the same `rng`.  All matrices come from ONE deterministic encoder-bank forward, one
+        dib_compression_matrices launch and ONE read-back (engine.compression_matrices); an engine without that method takes
+        the per-feature loop.  Nothing of the training state is touched.  Under torch.distributed every rank may call it:
+        there is no collective."""
+        from . import visualization
+        eng = self._ensure_engine()
+        on_device = isinstance(x_processed, torch.Tensor)
+        if x_raw is None:
+            x_raw = x_processed.detach().cpu().numpy() if on_device else np.asarray(x_processed)
+        sel = visualization.display_rows(x_raw, self.feature_dimensionalities, max_number_to_display, rng, cache)
+        F = self.number_features
+        if hasattr(eng, "compression_matrices"):
+            xd = x_processed if on_device and x_processed.device == eng.device and x_processed.dtype == torch.float32 \
+                else eng.to_device(x_processed if on_device else np.asarray(x_processed, dtype=np.float32))
+            if xd.dim() == 1:
+                xd = xd.view(-1, 1)
+            res = eng.compression_matrices(xd, sel["rows"], sel["n_rows"], want_distances=return_distances)
+            comp, dist = res if return_distances else (res, None)
+            mats = [comp[f, :n, :n] for f, n in enumerate(sel["n_rows"])]
+            dists = [dist[f, :n, :n] for f, n in enumerate(sel["n_rows"])] if return_distances else None
+        else:
+            xp = x_processed.detach().cpu().numpy() if on_device else np.asarray(x_processed)
+            split = np.split(xp.reshape(xp.shape[0], -1), np.cumsum(self.feature_dimensionalities)[:-1], axis=-1)
+            pairs = [visualization.encoded_compression_matrix(self.feature_encoders[f], split[f][sel["indices"][f]], self)
+                     for f in range(F)]
+            mats, dists = [p[0] for p in pairs], [p[1] for p in pairs]
+        out = []
+        for f in range(F):
+            d = dict(matrix=mats[f], indices=sel["indices"][f], values=sel["values"][f], counts=sel["counts"][f])
+            if return_distances:
+                d["distances"] = dists[f]
+            out.append(d)
+        return out
+
     # ---- compile / fit ---------------------------------------------------------------------
     def compile(self, optimizer='adam', loss=None, metrics=None, **_):
         """reference train.py:138-142."""
@@ -747,16 +792,39 @@ class SaveCompressionMatricesCallback(Callback):
     deterministically, Bhattacharyya matrix -> exp(-D) -> PNG named
     feature_{f}_log10beta_{log10(beta):.3f}.png (models.py:181).  The matrices are also kept in
     `self.matrices[(epoch, f)]`.
+
+    one_launch=True evaluates all features together - one `model.compression_matrices` call per save: the same display rows
+    (the same draws of numpy's global generator), one encoder-bank forward, one matrices launch and one read-back instead of
+    an encode, a distance launch and two read-backs per feature.  The validation matrix is uploaded once, and what the display
+    rule decides once per feature - the selection of a feature with < 10 unique values, which is deterministic, or that the
+    feature is drawn at random - is kept between saves (visualization.display_rows `cache`).
     """
 
-    def __init__(self, save_frequency, x_processed, x_raw, outdir, save_png=True):
+    def __init__(self, save_frequency, x_processed, x_raw, outdir, save_png=True, one_launch=False):
         super().__init__()
         self.save_frequency = save_frequency
         self.x_processed = np.asarray(x_processed)
         self.x_raw = np.asarray(x_raw)
         self.outdir = outdir
         self.save_png = save_png
+        self.one_launch = bool(one_launch)
+        self._x_dev = None
+        self._selection_cache = {}
         self.matrices = {}
+        self.betas = {}   # epoch of a save -> beta
+
+    def _save_one_launch(self, epoch, beta_value):
+        from . import visualization
+        eng = self.model._ensure_engine()
+        if self._x_dev is None and hasattr(eng, "compression_matrices"):   # uploaded once (the per-feature loop reads the host copy)
+            self._x_dev = eng.to_device(np.asarray(self.x_processed, dtype=np.float32))
+        res = self.model.compression_matrices(self._x_dev if self._x_dev is not None else self.x_processed, self.x_raw,
+                                              cache=self._selection_cache)
+        for feature_ind, r in enumerate(res):
+            if self.save_png:
+                out_fname = os.path.join(self.outdir, f'feature_{feature_ind}_log10beta_{np.log10(beta_value):.3f}.png')
+                visualization.draw_compression_matrix(r["matrix"], r["values"], r["counts"], out_fname)
+            self.matrices[(epoch, feature_ind)] = r["matrix"]
 
     def on_epoch_end(self, epoch, logs=None):
         if (epoch % self.save_frequency) != 0:
@@ -766,6 +834,10 @@ class SaveCompressionMatricesCallback(Callback):
         if rank != 0:
             return
         beta_value = float(self.model.beta.value())
+        self.betas[epoch] = beta_value
+        if self.one_launch:
+            os.makedirs(self.outdir, exist_ok=True)
+            return self._save_one_launch(epoch, beta_value)
         dims = self.model.feature_dimensionalities
         idx = np.cumsum(dims)[:-1]
         features_split = np.split(self.x_processed, idx, axis=-1)

@@ -3,8 +3,10 @@
 Mirrors reference train.py:12-178 (same flag names and defaults; the argparse `type=bool` trap and the
 `infonce_space_dimensionality` typo of the reference are fixed): dataset dict ->
 DistributedIBNet -> compile -> callbacks -> fit -> History post-processing (beta / KL in bits / loss without
-the KL term) -> distributed information plane PNG.  The InfoNCE custom loop (train.py:180-289) is a
-"next" row and is rejected explicitly.
+the KL term) -> distributed information plane PNG.  `--infonce_loss True` runs the InfoNCE custom loop
+(train.py:180-289, infonce.fit_infonce).  Both paths save the compression matrices every
+`--save_compression_matrices_frequency` epochs (train.py:163-166, 251-261): feature by feature or, with
+`--compression_matrices_one_launch True`, all features from one evaluation.
 
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N -m dib_amd.train ...`; every rank
 runs the same script, gradients are all-reduced over RCCL.
@@ -40,6 +42,9 @@ def get_args(argv=None):
     p.add_argument('--feature_embedding_dimension', type=int, default=32)
     p.add_argument('--optimizer', type=str, default='adam')
     p.add_argument('--save_compression_matrices_frequency', type=int, default=0)
+    p.add_argument('--compression_matrices_one_launch', type=_bool, default=False,
+                   help='evaluate the compression matrices of all features from one encoder-bank forward and one launch per '
+                        'save instead of feature by feature')
     p.add_argument('--info_bounds_frequency', type=int, default=0,
                    help='every N epochs: InfoNCE / leave-one-out bounds of every feature on the validation inputs '
                         '(info_bounds.npz + distributed_info_plane_mi.png in --artifact_outdir); 0 = off')
@@ -83,6 +88,15 @@ def postprocess_history(h, number_features, loss_is_info_based):
                 loss_validation=loss_series_validation)
 
 
+def save_compression_matrices_npz(saver, outdir):
+    """compression_matrices.npz of a SaveCompressionMatricesCallback: `epochs` and `beta` of its saves and one array
+    `epoch{e}_feature{f}` per matrix."""
+    epochs = sorted(saver.betas)
+    np.savez(os.path.join(outdir, 'compression_matrices.npz'), epochs=np.int64(epochs),
+             beta=np.float32([saver.betas[e] for e in epochs]),
+             **{f'epoch{e}_feature{f}': m for (e, f), m in saver.matrices.items()})
+
+
 def main(argv=None):
     from . import data, models, optimizers, visualization
     args = get_args(argv)
@@ -117,9 +131,17 @@ def main(argv=None):
         feature_embedding_dimension=args.feature_embedding_dimension,
         output_activation_fn=dataset_dict['output_activation_fn'] if not args.infonce_loss else None,
         noise_seed=args.seed, init_seed=args.seed, shuffle_seed=args.seed)
+    saver = None
+    if args.save_compression_matrices_frequency > 0:
+        saver = models.SaveCompressionMatricesCallback(
+            args.save_compression_matrices_frequency, dataset_dict['x_valid'],
+            dataset_dict.get('x_valid_raw', dataset_dict['x_valid']), args.artifact_outdir,
+            one_launch=args.compression_matrices_one_launch)
     if args.infonce_loss:  # ---- custom training loop, reference train.py:180-289 ----
         from . import infonce
         F = dataset_dict['number_features']
+        if saver is not None:
+            saver.set_model(model)
         out = infonce.fit_infonce(
             model, dataset_dict['x_train'], dataset_dict['y_train'], dataset_dict['x_valid'], dataset_dict['y_valid'],
             batch_size=args.batch_size, number_pretraining_epochs=args.number_pretraining_epochs,
@@ -128,7 +150,9 @@ def main(argv=None):
             shared_dimensionality=args.infonce_shared_dimensionality, similarity=args.infonce_similarity,
             temperature=args.infonce_temperature, use_positional_encoding=args.use_positional_encoding,
             number_positional_encoding_frequencies=args.number_positional_encoding_frequencies, activation_fn=activation,
-            seed=args.seed)
+            seed=args.seed,
+            # train.py:245-261: the matrices at the epoch boundaries, named by the beta just assigned
+            epoch_callback=(lambda epoch, _model: saver.on_epoch_end(epoch)) if saver is not None else None)
         # train.py:271-286: KL and (info based) losses to bits
         kl_series, kl_series_validation = out['kl'] / np.log(2), out['kl_validation'] / np.log(2)
         loss_series, loss_series_validation = out['loss_infonce'], out['loss_infonce_validation']
@@ -139,16 +163,16 @@ def main(argv=None):
             np.savez(os.path.join(args.artifact_outdir, 'history.npz'), beta=np.float32(out['beta']), kl_bits=kl_series,
                      loss=loss_series, kl_bits_validation=kl_series_validation, loss_validation=loss_series_validation)
             visualization.save_distributed_info_plane(kl_series_validation, loss_series_validation, args.artifact_outdir)
+            if saver is not None:
+                save_compression_matrices_npz(saver, args.artifact_outdir)
         return out
     optimizer = optimizers.get(args.optimizer)
     optimizer.learning_rate = args.learning_rate  # train.py:128-129
     model.compile(optimizer=optimizer, loss=dataset_dict['loss'], metrics=dataset_dict['metrics'])
     callbacks = [models.InfoBottleneckAnnealingCallback(args.beta_start, args.beta_end, args.number_pretraining_epochs,
                                                         args.number_annealing_epochs)]
-    if args.save_compression_matrices_frequency > 0:
-        callbacks.append(models.SaveCompressionMatricesCallback(
-            args.save_compression_matrices_frequency, dataset_dict['x_valid'],
-            dataset_dict.get('x_valid_raw', dataset_dict['x_valid']), args.artifact_outdir))
+    if saver is not None:
+        callbacks.append(saver)
     history = model.fit(dataset_dict['x_train'], dataset_dict['y_train'], epochs=number_epochs, shuffle=True,
                         batch_size=args.batch_size, callbacks=callbacks, verbose=args.verbose,
                         validation_data=(dataset_dict['x_valid'], dataset_dict['y_valid']),
@@ -161,6 +185,8 @@ def main(argv=None):
         np.savez(os.path.join(args.artifact_outdir, 'history.npz'), beta=beta_series, kl_bits=kl_series,
                  loss=loss_series, kl_bits_validation=kl_series_validation, loss_validation=loss_series_validation)
         visualization.save_distributed_info_plane(kl_series_validation, loss_series_validation, args.artifact_outdir)
+        if saver is not None:
+            save_compression_matrices_npz(saver, args.artifact_outdir)
         if history.information is not None:
             info = history.information
             np.savez(os.path.join(args.artifact_outdir, 'info_bounds.npz'), epochs=np.int64(info['epochs']),

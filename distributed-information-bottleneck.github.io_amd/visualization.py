@@ -31,11 +31,99 @@ def select_display_inputs(inp_features_raw, max_number_to_display=128, rng=None)
     if len(unique_vals) < 10:
         counts = [np.average(raw == v) for v in unique_vals]
         return unique_idx[np.argsort(unique_vals)], np.sort(unique_vals), counts
+    return _draw_display_inputs(raw, max_number_to_display, rng)
+
+
+def _draw_display_inputs(raw, max_number_to_display, rng):
+    """the random branch of select_display_inputs: `max_number_to_display` rows drawn with replacement, sorted by raw value"""
     rng = rng or np.random
     sel = rng.choice(raw.shape[0], max_number_to_display)
     flat = raw[sel].reshape(len(sel), -1)[:, 0]
     order = np.argsort(flat)
     return sel[order], flat[order], None
+
+
+def display_rows(x_raw, feature_dimensionalities, max_number_to_display=128, rng=None, cache=None):
+    """The display sample of EVERY feature by the host rule: select_display_inputs on the columns of features 0 .. F-1 of
+    x_raw [N, sum d_f], in that order - with the same `rng` exactly the rows the per-feature loop of
+    SaveCompressionMatricesCallback draws.  Returns a dict:
+      "indices" / "values" / "counts": per feature what select_display_inputs returns (row indices, sorted raw values, value
+                 frequencies or None);
+      "rows":    int32 [F, n_max], feature f's indices padded to the longest sample with its own first index;
+      "n_rows":  int32 [F], the sample sizes (the `counts` of engine.compression_matrices).
+    `cache` (a dict the caller keeps between calls on the same x_raw) stores what does not change from call to call: the
+    selections of features with < 10 unique values - they are deterministic and consume no random draw - and, for the others,
+    that they are drawn at random (cache[f] = None): a later call draws them without sorting the whole column for np.unique
+    again, with the same draws of `rng`."""
+    x_raw = np.asarray(x_raw)
+    if x_raw.ndim == 1:
+        x_raw = x_raw.reshape(-1, 1)
+    dims = [int(d) for d in feature_dimensionalities]
+    split = np.split(x_raw, np.cumsum(dims)[:-1], axis=-1)
+    sel = []
+    for f, raw_f in enumerate(split):
+        if cache is not None and f in cache:
+            s = cache[f] if cache[f] is not None else _draw_display_inputs(raw_f, max_number_to_display, rng)
+        else:
+            s = select_display_inputs(raw_f, max_number_to_display, rng)
+            if cache is not None:
+                cache[f] = s if s[2] is not None else None
+        sel.append(s)
+    n_rows = np.asarray([len(s[0]) for s in sel], dtype=np.int32)
+    rows = np.empty((len(sel), max(1, int(n_rows.max()))), dtype=np.int32)
+    for f, s in enumerate(sel):
+        rows[f] = s[0][0] if len(s[0]) else 0
+        rows[f, :len(s[0])] = s[0]
+    return dict(indices=[s[0] for s in sel], values=[s[1] for s in sel], counts=[s[2] for s in sel], rows=rows, n_rows=n_rows)
+
+
+def encoded_compression_matrix(feature_encoder, inputs, model=None):
+    """(exp(-D), D) for D the Bhattacharyya distances between the Gaussians feature_encoder assigns to `inputs` [n, d_f]: the
+    model engine's kernel when it has one, else utils.bhattacharyya_dist_mat."""
+    enc = np.asarray(feature_encoder(inputs))
+    emb_mus, emb_logvars = np.split(enc, 2, axis=-1)
+    if model is not None and getattr(model, "_engine", None) is not None and hasattr(model._engine, "bhattacharyya"):
+        bhat = model._engine.bhattacharyya(emb_mus, emb_logvars, emb_mus, emb_logvars).detach().cpu().numpy()
+    else:
+        bhat = utils.bhattacharyya_dist_mat(emb_mus, emb_logvars, emb_mus, emb_logvars)
+    return np.exp(-bhat), bhat
+
+
+def draw_compression_matrix(matrix, sorted_raw, counts, out_fname, feature_label=None):
+    """The figure of one compression matrix: the matrix, and along its left and top edges the displayed raw values (a curve
+    over the sample, or the value histogram when `counts` - the value frequencies - is given).  Saved to out_fname."""
+    plt = _plt()
+    n = len(sorted_raw)
+    fig = plt.figure(figsize=(6, 6))
+    gs = fig.add_gridspec(2, 2, width_ratios=(1, 2), height_ratios=(1, 2), left=0.1, right=0.9, bottom=0.1,
+                          top=0.9, wspace=0.05, hspace=0.05)
+    ax = fig.add_subplot(gs[1, 1])
+    ax.imshow(matrix, vmin=0, vmax=1, cmap='Blues_r')
+    ax.axis('off')
+    axl = fig.add_subplot(gs[1, 0])
+    axt = fig.add_subplot(gs[0, 1])
+    if counts is not None:
+        axl.barh(sorted_raw, counts, height=0.8)
+        axt.bar(sorted_raw, counts, width=0.8)
+        axl.set_xlim(0, 1)
+        axt.set_ylim(0, 1)
+    else:
+        axl.plot(sorted_raw, np.arange(n), 'k', lw=3)
+        axl.set_ylim(n, 0)
+        axt.plot(np.arange(n), sorted_raw, 'k', lw=3)
+        axt.set_xlim(0, n)
+    for a in (axl, axt):
+        a.set_xticks([]) if a is axt or counts is not None else None
+        a.set_yticks([]) if a is axl and counts is None else None
+        for s in ('right', 'top'):
+            a.spines[s].set_visible(False)
+    ax0 = fig.add_subplot(gs[0, 0])
+    ax0.text(0, 0, feature_label if feature_label is not None else '')
+    ax0.set_xlim(-0.5, 0.5)
+    ax0.set_ylim(-0.5, 0.5)
+    ax0.axis('off')
+    fig.savefig(out_fname)
+    plt.close(fig)
 
 
 def save_compression_matrices(feature_encoder, inp_features, out_fname, inp_features_raw=None, feature_label=None,
@@ -46,46 +134,9 @@ def save_compression_matrices(feature_encoder, inp_features, out_fname, inp_feat
     if inp_features_raw is None:
         inp_features_raw = inp_features
     inds, sorted_raw, counts = select_display_inputs(inp_features_raw, max_number_to_display, rng)
-    enc = np.asarray(feature_encoder(inp_features[inds]))
-    emb_mus, emb_logvars = np.split(enc, 2, axis=-1)
-    if model is not None and getattr(model, "_engine", None) is not None and hasattr(model._engine, "bhattacharyya"):
-        bhat = model._engine.bhattacharyya(emb_mus, emb_logvars, emb_mus, emb_logvars).detach().cpu().numpy()
-    else:
-        bhat = utils.bhattacharyya_dist_mat(emb_mus, emb_logvars, emb_mus, emb_logvars)
-    compression_matrix = np.exp(-bhat)
+    compression_matrix, _ = encoded_compression_matrix(feature_encoder, inp_features[inds], model)
     if out_fname:
-        plt = _plt()
-        n = len(sorted_raw)
-        fig = plt.figure(figsize=(6, 6))
-        gs = fig.add_gridspec(2, 2, width_ratios=(1, 2), height_ratios=(1, 2), left=0.1, right=0.9, bottom=0.1,
-                              top=0.9, wspace=0.05, hspace=0.05)
-        ax = fig.add_subplot(gs[1, 1])
-        ax.imshow(compression_matrix, vmin=0, vmax=1, cmap='Blues_r')
-        ax.axis('off')
-        axl = fig.add_subplot(gs[1, 0])
-        axt = fig.add_subplot(gs[0, 1])
-        if counts is not None:
-            axl.barh(sorted_raw, counts, height=0.8)
-            axt.bar(sorted_raw, counts, width=0.8)
-            axl.set_xlim(0, 1)
-            axt.set_ylim(0, 1)
-        else:
-            axl.plot(sorted_raw, np.arange(n), 'k', lw=3)
-            axl.set_ylim(n, 0)
-            axt.plot(np.arange(n), sorted_raw, 'k', lw=3)
-            axt.set_xlim(0, n)
-        for a in (axl, axt):
-            a.set_xticks([]) if a is axt or counts is not None else None
-            a.set_yticks([]) if a is axl and counts is None else None
-            for s in ('right', 'top'):
-                a.spines[s].set_visible(False)
-        ax0 = fig.add_subplot(gs[0, 0])
-        ax0.text(0, 0, feature_label if feature_label is not None else '')
-        ax0.set_xlim(-0.5, 0.5)
-        ax0.set_ylim(-0.5, 0.5)
-        ax0.axis('off')
-        fig.savefig(out_fname)
-        plt.close(fig)
+        draw_compression_matrix(compression_matrix, sorted_raw, counts, out_fname, feature_label)
     return compression_matrix
 
 

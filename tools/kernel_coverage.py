@@ -82,6 +82,9 @@ ORACLE_TESTS = {
         "test_kernel_matches_oracle_across_the_envelope", "test_far_apart_gaussians_and_duplicated_rows",
         "test_information_per_feature_matches_oracle_on_every_dispatch_path",
         "test_validation_set_smaller_than_the_batch_draws_with_replacement"},
+    "test_gpu_compression_matrices.py": {
+        "test_kernel_matches_the_float64_oracle", "test_gather_equals_numpy",
+        "test_model_matches_the_float64_chain_no_worse_than_the_loop"},
 }
 # tests that demand the bits (or fp32 summation-order tolerance) of a path the tests above check against an oracle
 EQUIVALENCE_TESTS = {
@@ -116,6 +119,11 @@ EQUIVALENCE_TESTS = {
         "test_all_features_equal_the_per_feature_loop_and_a_shape_beyond_the_envelope_takes_it",
         "test_callback_in_one_launch_fills_bounds_like_information_per_feature",
         "test_tracked_fit_trains_exactly_like_the_untracked_fit"},
+    "test_gpu_compression_matrices.py": {
+        "test_matrices_equal_their_transposes_bit_for_bit", "test_one_output_alone_gives_the_same_bits",
+        "test_replay_placement_and_feature_splits_are_bit_identical",
+        "test_a_shape_beyond_the_envelope_takes_the_loop_and_equals_it",
+        "test_callback_one_launch_and_loop_agree_and_neither_changes_the_training"},
 }
 
 
