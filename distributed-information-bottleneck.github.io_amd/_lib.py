@@ -276,6 +276,22 @@ SIGNATURES_COMPRESSION = {
 }
 
 
+# include/dib_optimizers.h: the Keras optimizer family beyond Adam and momentum-free SGD on a flat buffer
+class OptimizerHyper(ctypes.Structure):
+    """dib_optimizer_hyper"""
+    _fields_ = [("rho", c_float), ("beta_2", c_float), ("epsilon", c_float), ("momentum", c_float),
+                ("initial_accumulator", c_float), ("nesterov", c_int32), ("centered", c_int32), ("reserved", c_int32)]
+
+
+SIGNATURES_OPTIMIZERS = {
+    "dib_optimizer_slots": (c_int, [c_int, POINTER(OptimizerHyper)]),
+    "dib_optimizer_init": (c_int, [c_int, POINTER(OptimizerHyper), c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "dib_optimizer_step": (c_int, [c_int, POINTER(OptimizerHyper), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                   c_void_p, c_void_p, c_void_p, c_float, c_void_p]),
+    "dib_optimizer_advance": (c_int, [c_int, POINTER(OptimizerHyper), c_void_p, c_void_p, c_void_p]),
+}
+
+
 def load_library(build_if_missing: bool = True):
     """dlopen libdib_hip.so and attach signatures.  Raises (no fallback) if it cannot be loaded."""
     global _lib
@@ -312,7 +328,7 @@ def _attach(lib):
                            "rebuild it (python -c 'import __graft_entry__ as g; g.build()' / tools/build_variant.sh)")
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_ST.items()) + list(SIGNATURES_MEASURE.items()) \
             + list(SIGNATURES_CIRCUIT.items()) + list(SIGNATURES_PARTITION.items()) + list(SIGNATURES_MI_CHANNEL.items()) + list(SIGNATURES_MI_FEATURES.items()) \
-            + list(SIGNATURES_COMPRESSION.items()):
+            + list(SIGNATURES_COMPRESSION.items()) + list(SIGNATURES_OPTIMIZERS.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

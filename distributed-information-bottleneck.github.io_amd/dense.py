@@ -259,3 +259,46 @@ class DenseStack:
         check(self.lib.dib_adam_step(_ptr(self.params), _ptr(self.grads), _ptr(self.adam_m), _ptr(self.adam_v),
                                      self.n_params, _ptr(self.lr_dev), _ptr(self.t_dev), beta1, beta2, eps, 1.0,
                                      self.eng._stream()), "dib_adam_step")
+
+    def optimizer_step(self, opt, lr: Optional[float] = None) -> None:
+        """One update by any optimizers.Optimizer (the custom loop steps both networks with one Keras optimizer, reference
+        train.py:196,219).  Slabs a backward(reduce=False) left are summed first.  Adam: adam_step, its launches and bits; plain
+        SGD: dib_sgd_step; every other rule: dib_optimizer_step + dib_optimizer_advance (include/dib_optimizers.h) on this
+        stack's own state - adam_m, adam_v, a third buffer allocated when a rule first needs it, its step count and Nadam's P.
+        A change of rule re-initialises that state."""
+        if lr is not None:
+            self.lr_dev.fill_(float(lr))
+        if opt.native and opt.name == "adam":
+            self.adam_step(None, opt.beta_1, opt.beta_2, opt.epsilon, fused_reduce=self._unreduced is not None)
+            return
+        st = self.eng._stream()
+        pl = self._unreduced
+        if pl is not None:
+            check(self.lib.dib_reduce_splits(_ptr(pl["slabs"]), self.n_params, pl["nsplit"], self.n_params, _ptr(self.grads), st),
+                  "dib_reduce_splits")
+            self._unreduced = None
+        if opt.native:
+            check(self.lib.dib_sgd_step(_ptr(self.params), _ptr(self.grads), self.n_params, _ptr(self.lr_dev), 1.0, st), "dib_sgd_step")
+            return
+        from ._lib import OptimizerHyper
+        hyper = OptimizerHyper(**opt.hyper())
+        slots = opt.slots()
+        if slots > 2 and getattr(self, "opt_s2", None) is None:
+            self.opt_s2 = torch.zeros_like(self.adam_m)
+        bufs = (self.adam_m, self.adam_v, getattr(self, "opt_s2", None))
+        state = [_ptr(bufs[k]) if k < slots else None for k in range(3)]
+        scalar = None
+        if opt.name == "nadam":
+            if getattr(self, "opt_scalar", None) is None:
+                self.opt_scalar = torch.ones(1, dtype=torch.float64, device=self.device)
+            scalar = self.opt_scalar
+        key = (opt.kind, tuple(sorted(opt.hyper().items())))
+        if getattr(self, "_opt_key", None) != key:
+            check(self.lib.dib_optimizer_init(opt.kind, ctypes.byref(hyper), *state, self.n_params, _ptr(scalar), st),
+                  "dib_optimizer_init")
+            self.t_dev.zero_()
+            self._opt_key = key
+        check(self.lib.dib_optimizer_step(opt.kind, ctypes.byref(hyper), _ptr(self.params), _ptr(self.grads), *state, self.n_params,
+                                          _ptr(self.lr_dev), _ptr(self.t_dev), _ptr(scalar), 1.0, st), "dib_optimizer_step")
+        check(self.lib.dib_optimizer_advance(opt.kind, ctypes.byref(hyper), _ptr(self.t_dev), _ptr(scalar), st),
+              "dib_optimizer_advance")

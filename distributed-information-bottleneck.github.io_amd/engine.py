@@ -172,9 +172,78 @@ class HipEngine:
         return self.grads.detach().cpu().numpy().copy()
 
     def reset_optimizer(self) -> None:
-        self.adam_m.zero_()
-        self.adam_v.zero_()
+        """optimizer state as before the first step, by the bound rule (set_optimizer): zeros and t = 0 for Adam / plain SGD;
+        the rule's own start values otherwise (Adagrad's accumulator, Nadam's P = 1: dib_optimizer_init)"""
+        opt = getattr(self, "_opt", None)
+        if opt is None:
+            self.adam_m.zero_()
+            self.adam_v.zero_()
+        else:
+            s = self._opt_state(opt)
+            check(self.lib.dib_optimizer_init(opt.kind, byref(self._opt_hyper(opt)), *(_ptr(b) for b in s), self.adam_m.numel(),
+                                              _ptr(self._opt_scalar(opt)), self._stream()), "dib_optimizer_init")
         self.t_dev.zero_()
+
+    # ---- the optimizer family beyond Adam / momentum-free SGD (include/dib_optimizers.h) ------------------------------------
+    @staticmethod
+    def _opt_hyper(opt) -> "_lib.OptimizerHyper":
+        return _lib.OptimizerHyper(**opt.hyper())
+
+    @staticmethod
+    def _opt_key(opt):
+        return None if opt is None or opt.native else (opt.kind, tuple(sorted(opt.hyper().items())))
+
+    def _opt_state(self, opt):
+        """the rule's state slots in order: adam_m, adam_v and a third buffer allocated when a rule first needs it"""
+        slots = opt.slots()
+        if slots > 2 and getattr(self, "opt_s2", None) is None:
+            self.opt_s2 = torch.zeros_like(self.adam_m)
+        bufs = (self.adam_m, self.adam_v, getattr(self, "opt_s2", None))
+        return [bufs[k] if k < slots else None for k in range(3)]
+
+    def _opt_scalar(self, opt):
+        """Nadam's running product P of its momentum schedule: one device float64 (None for every other rule)"""
+        if opt.name != "nadam":
+            return None
+        if getattr(self, "opt_scalar", None) is None:
+            self.opt_scalar = torch.ones(1, dtype=torch.float64, device=self.device)
+        return self.opt_scalar
+
+    def set_optimizer(self, opt) -> None:
+        """Bind an optimizers.Optimizer: the state buffers change meaning with the rule, so a CHANGE of rule (kind or
+        hyper-parameters; the learning rate is not one) re-initialises them and the step count.  Binding the rule already bound is
+        free; Adam and momentum-free SGD (`opt.native`) are the engine's initial binding."""
+        key = self._opt_key(opt)
+        if key == self._opt_key(getattr(self, "_opt", None)):
+            return
+        self._opt = None if key is None else opt
+        self.reset_optimizer()
+
+    def optimizer_step_range(self, opt, offset: int, count: int, grad_scale: float = 1.0) -> None:
+        """the rule on the elements [offset, offset + count) of the flat buffers: one launch, reads t and P, writes neither"""
+        sl = lambda b: None if b is None else b[offset:]
+        s = [sl(b) for b in self._opt_state(opt)]
+        check(self.lib.dib_optimizer_step(opt.kind, byref(self._opt_hyper(opt)), _ptr(sl(self.params)), _ptr(sl(self.grads)),
+                                          *(_ptr(b) for b in s), int(count), _ptr(self.lr_dev), _ptr(self.t_dev),
+                                          _ptr(self._opt_scalar(opt)), float(grad_scale), self._stream()), "dib_optimizer_step")
+
+    def optimizer_advance(self, opt) -> None:
+        """ends a step of the rule: t += 1 (and Nadam's P) in a one-thread launch, after every range has been stepped"""
+        check(self.lib.dib_optimizer_advance(opt.kind, byref(self._opt_hyper(opt)), _ptr(self.t_dev), _ptr(self._opt_scalar(opt)),
+                                             self._stream()), "dib_optimizer_advance")
+
+    def optimizer_step(self, opt, grad_scale: float = 1.0) -> None:
+        """One update of the whole flat buffer from self.grads by any optimizers.Optimizer: Adam and momentum-free SGD through
+        adam_step / sgd_step (their launches and bits), every other rule through dib_optimizer_step + dib_optimizer_advance."""
+        self.set_optimizer(opt)
+        if opt.native:
+            if opt.name == "adam":
+                self.adam_step(opt.beta_1, opt.beta_2, opt.epsilon, grad_scale)
+            else:
+                self.sgd_step(grad_scale)
+            return
+        self.optimizer_step_range(opt, 0, self.n_params, grad_scale)
+        self.optimizer_advance(opt)
 
     def set_beta(self, v: float) -> None:
         self.beta_dev.fill_(float(v))
@@ -260,6 +329,12 @@ class HipEngine:
     def optimizer_step_part(self, batch: int, part: int, optimizer, bump: bool) -> None:
         """the optimizer on ONE gradient bucket (after its all-reduce): the data-parallel fit steps buckets 1 and 2 while
         bucket 3 is still on the wire; the launch with bump=True (the last) advances Adam's step count."""
+        if optimizer[0] == "opt":   # ("opt", Optimizer): a rule of include/dib_optimizers.h - a range launch, the advance with the last
+            off, cnt = self.part_range(part)
+            self.optimizer_step_range(optimizer[1], off, cnt)
+            if bump:
+                self.optimizer_advance(optimizer[1])
+            return
         self.step_tail(batch, part, _lib.TAIL_BUMP if (bump and optimizer[0] == "adam") else 0, optimizer=optimizer)
 
     def part_range(self, part: int):
@@ -360,6 +435,13 @@ class HipEngine:
         self.grads, ready for the data-parallel all-reduce(sum) and the optimizer step.  optimizer=("adam", b1, b2, eps) /
         ("sgd",) (single process only): the update is applied by the step's LAST launch, which also reduces the gradient
         partials, sums the KL / loss partials and accumulates the History metrics (csrc/dib_tail.h)."""
+        if optimizer is not None and optimizer[0] == "opt":
+            # ("opt", Optimizer), a rule of include/dib_optimizers.h: the step ends with the tail WITHOUT an optimizer flag, then
+            # the rule's launch over the whole buffer, then its advance (two launches more than Adam's fused tail)
+            self.train_step(x, y, row_idx, row0, batch, seed, step, loss_kind, inv_global_batch, accumulate,
+                            on_integration_grads_ready, on_encoder_front_grads_ready, None)
+            self.optimizer_step(optimizer[1])
+            return
         inv = 1.0 / batch if inv_global_batch is None else inv_global_batch
         kind = LOSS_KINDS[loss_kind]
         fused_head = self._head_fused(kind)

@@ -171,14 +171,20 @@ def fit_infonce(model, x_train, y_train, x_valid, y_valid, *, batch_size: int, n
                 temperature: float = 1.0, use_positional_encoding: bool = True,
                 number_positional_encoding_frequencies: int = 5, activation_fn: Optional[str] = 'relu', seed: int = 0,
                 epoch_callback=None, output_encoder: Optional[DenseStack] = None,
-                shuffle_buffer: int = SHUFFLE_BUFFER) -> Dict[str, np.ndarray]:
+                shuffle_buffer: int = SHUFFLE_BUFFER, optimizer=None) -> Dict[str, np.ndarray]:
     """Returns dict(beta, kl [epochs-1, F] nats, loss_infonce, kl_validation, loss_infonce_validation) - the series the
     reference builds at train.py:237-279 (before its conversion to bits) - plus kl_total / kl_total_validation.
     The reference's own KL series is `kl_loss / model.beta` with kl_loss = model.losses, the one-element list
     [beta * sum_f KL_f] (models.py:118): ITS series are the row sums kl_total; the per-feature columns are this project's
     superset.  `output_encoder`: a pre-built Y encoder (default: a fresh DenseStack seeded with seed + 1).  `shuffle_buffer`: the
-    reference's 10 000 (train.py:227); tools/stream_effect.py passes the dataset length to measure what the buffer does."""
+    reference's 10 000 (train.py:227); tools/stream_effect.py passes the dataset length to measure what the buffer does.
+    `optimizer`: an optimizers.Optimizer or a Keras name (reference train.py:128-129 builds ONE optimizer for both branches); both
+    networks step with it and with the same step count, at `learning_rate`.  None: Keras-Adam defaults, today's launches."""
     eng = model._ensure_engine()
+    from . import optimizers as _optimizers
+    opt = None if optimizer is None else _optimizers.get(optimizer)
+    if opt is not None:
+        eng.set_optimizer(opt)
     assert model.output_dimensionality == shared_dimensionality, "model output must be the shared embedding space"
     F = model.number_features
     xd, yd = eng.to_device(np.asarray(x_train, dtype=np.float32)), eng.to_device(np.asarray(y_train, dtype=np.float32))
@@ -229,6 +235,9 @@ def fit_infonce(model, x_train, y_train, x_valid, y_valid, *, batch_size: int, n
 
     from . import _lib
     adam = ("adam", 0.9, 0.999, 1e-7)                             # tf.keras.optimizers.Adam defaults (train.py:128-129)
+    if opt is not None and opt.native and opt.name == "adam":
+        adam = ("adam", opt.beta_1, opt.beta_2, opt.epsilon)
+    tail_opt = adam if opt is None or (opt.native and opt.name == "adam") else None   # Adam rides in the step's tail launch
     slots = _LossSlots(eng.device, eng.metrics_acc.dtype)
     # single process: the per-feature KL of every step is accumulated on the device by the step's LAST launch (metrics_acc[f] +=
     # KL_f sum / B, dib_step_tail) - training and validation into accumulators of THIS loop, read once per epoch boundary.
@@ -253,10 +262,14 @@ def fit_infonce(model, x_train, y_train, x_valid, y_valid, *, batch_size: int, n
             if training:
                 compb = yenc.companion_backward(gy) if comp is not None else None
                 eng.backward_from_pred_grad(gx, idx, 0, B, model.noise_seed, step, inv_global_batch=1.0 / batch_size,
-                                            finish_flags=_lib.TAIL_KL | _lib.TAIL_METRICS, optimizer=adam, metrics_acc=kl_acc["kl"],
+                                            finish_flags=_lib.TAIL_KL | _lib.TAIL_METRICS, optimizer=tail_opt, metrics_acc=kl_acc["kl"],
                                             **({} if compb is None else dict(companion=compb)))
                 yenc.backward(gy, reduce=False, **({} if compb is None else dict(dgrad_done=True)))
-                yenc.adam_step(fused_reduce=True)                  # one Keras Adam over all variables (train.py:196,219)
+                if tail_opt is not None:
+                    yenc.adam_step(None, *adam[1:], fused_reduce=True)   # one Keras Adam over all variables (train.py:196,219)
+                else:                                              # any other rule: the same optimizer, the same t, both networks
+                    eng.optimizer_step(opt)
+                    yenc.optimizer_step(opt)
             else:
                 eng.step_tail(B, -1, _lib.TAIL_KL | _lib.TAIL_METRICS, 1.0 / batch_size, metrics_acc=kl_acc["kl_validation"])
             return loss, None
@@ -273,8 +286,12 @@ def fit_infonce(model, x_train, y_train, x_valid, y_valid, *, batch_size: int, n
             yenc.backward(gy)
             dist.all_reduce(eng.grads)
             dist.all_reduce(yenc.grads)
-            eng.adam_step()                                        # one Keras Adam over all variables (train.py:196,219)
-            yenc.adam_step()
+            if opt is None:
+                eng.adam_step()                                    # one Keras Adam over all variables (train.py:196,219)
+                yenc.adam_step()
+            else:
+                eng.optimizer_step(opt)
+                yenc.optimizer_step(opt)
         return loss, kl
 
     def epoch_mean(name, values):

@@ -387,13 +387,19 @@ class DistributedIBNet:
         return None, 0, 1
 
     def _optimizer_tuple(self):
+        """what HipEngine.train_step / optimizer_step_part take: Adam and momentum-free SGD ride in the step tail; every other
+        rule (optimizers.Optimizer.native is False) is ("opt", optimizer): dib_optimizer_step + dib_optimizer_advance"""
         opt = self.optimizer
+        if not opt.native:
+            return ("opt", opt)
         return ("adam", opt.beta_1, opt.beta_2, opt.epsilon) if opt.name == "adam" else ("sgd",)
 
     def _optimizer_step(self, eng):
         opt = self.optimizer
         eng.set_lr(opt.learning_rate)
-        if opt.name == "adam":
+        if not opt.native:
+            eng.optimizer_step(opt)
+        elif opt.name == "adam":
             eng.adam_step(opt.beta_1, opt.beta_2, opt.epsilon)
         else:
             eng.sgd_step()
@@ -493,7 +499,13 @@ class DistributedIBNet:
         # eager (4.09 vs 3.76 ms/epoch, tools/small_batch_bench.py) - the step is bound by the latency of its dependent
         # kernels, not by launch overhead.
         n_full = n // bs
+        if hasattr(eng, "set_optimizer"):
+            eng.set_optimizer(self.optimizer)   # a change of rule re-initialises the optimizer state; the same rule: nothing
+        elif not self.optimizer.native:
+            raise ValueError(f"optimizer {self.optimizer.name!r} needs the HIP engine (include/dib_optimizers.h)")
+        # (the rules of include/dib_optimizers.h always run eagerly: their step is not part of capture_step_graph)
         use_graphs = (dist is None and hasattr(eng, "capture_step_graph") and bs <= 8192 and n_full * epochs >= 64
+                      and self.optimizer.native
                       and os.environ.get("DIB_ENABLE_GRAPHS", "0") == "1")
         graphs = {}
         if use_graphs:

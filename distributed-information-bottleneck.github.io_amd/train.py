@@ -40,7 +40,8 @@ def get_args(argv=None):
     p.add_argument('--use_positional_encoding', type=_bool, default=True)
     p.add_argument('--activation_fn', type=str, default='relu')
     p.add_argument('--feature_embedding_dimension', type=int, default=32)
-    p.add_argument('--optimizer', type=str, default='adam')
+    p.add_argument('--optimizer', type=str, default='adam',
+                   help='a Keras optimizer name: adam, sgd, rmsprop, adagrad, adadelta, adamax, nadam (Keras defaults)')
     p.add_argument('--save_compression_matrices_frequency', type=int, default=0)
     p.add_argument('--compression_matrices_one_launch', type=_bool, default=False,
                    help='evaluate the compression matrices of all features from one encoder-bank forward and one launch per '
@@ -137,6 +138,8 @@ def main(argv=None):
             args.save_compression_matrices_frequency, dataset_dict['x_valid'],
             dataset_dict.get('x_valid_raw', dataset_dict['x_valid']), args.artifact_outdir,
             one_launch=args.compression_matrices_one_launch)
+    optimizer = optimizers.get(args.optimizer)  # any Keras name; both branches train with it (train.py:128-129, 196, 219)
+    optimizer.learning_rate = args.learning_rate
     if args.infonce_loss:  # ---- custom training loop, reference train.py:180-289 ----
         from . import infonce
         F = dataset_dict['number_features']
@@ -150,7 +153,7 @@ def main(argv=None):
             shared_dimensionality=args.infonce_shared_dimensionality, similarity=args.infonce_similarity,
             temperature=args.infonce_temperature, use_positional_encoding=args.use_positional_encoding,
             number_positional_encoding_frequencies=args.number_positional_encoding_frequencies, activation_fn=activation,
-            seed=args.seed,
+            seed=args.seed, optimizer=optimizer,
             # train.py:245-261: the matrices at the epoch boundaries, named by the beta just assigned
             epoch_callback=(lambda epoch, _model: saver.on_epoch_end(epoch)) if saver is not None else None)
         # train.py:271-286: KL and (info based) losses to bits
@@ -166,8 +169,6 @@ def main(argv=None):
             if saver is not None:
                 save_compression_matrices_npz(saver, args.artifact_outdir)
         return out
-    optimizer = optimizers.get(args.optimizer)
-    optimizer.learning_rate = args.learning_rate  # train.py:128-129
     model.compile(optimizer=optimizer, loss=dataset_dict['loss'], metrics=dataset_dict['metrics'])
     callbacks = [models.InfoBottleneckAnnealingCallback(args.beta_start, args.beta_end, args.number_pretraining_epochs,
                                                         args.number_annealing_epochs)]

@@ -85,6 +85,9 @@ ORACLE_TESTS = {
     "test_gpu_compression_matrices.py": {
         "test_kernel_matches_the_float64_oracle", "test_gather_equals_numpy",
         "test_model_matches_the_float64_chain_no_worse_than_the_loop"},
+    "test_gpu_optimizers.py": {
+        "test_every_rule_matches_the_float64_restatement", "test_envelope_of_sizes",
+        "test_fit_with_rmsprop_matches_the_float64_oracle_fit", "test_fit_infonce_with_nadam_matches_the_float64_loop_oracle"},
 }
 # tests that demand the bits (or fp32 summation-order tolerance) of a path the tests above check against an oracle
 EQUIVALENCE_TESTS = {
@@ -124,6 +127,9 @@ EQUIVALENCE_TESTS = {
         "test_replay_placement_and_feature_splits_are_bit_identical",
         "test_a_shape_beyond_the_envelope_takes_the_loop_and_equals_it",
         "test_callback_one_launch_and_loop_agree_and_neither_changes_the_training"},
+    "test_gpu_optimizers.py": {
+        "test_buckets_then_one_advance_equal_the_whole_buffer_step",
+        "test_captured_steps_replay_bit_identically_and_advance_t_and_P"},
 }
 
 
