@@ -292,6 +292,22 @@ SIGNATURES_OPTIMIZERS = {
 }
 
 
+# include/dib_losses.h: the Keras loss and metric family beyond dib_loss_fwd_bwd's four kinds
+class LossDesc(ctypes.Structure):
+    """dib_loss_desc"""
+    _fields_ = [("kind", c_int32), ("metric", c_int32), ("param", c_float)]
+
+
+SIGNATURES_LOSSES = {
+    "dib_loss_ex_supported": (c_int, [POINTER(LossDesc), c_int]),
+    "dib_loss_ex_lanes": (c_int, [c_int]),
+    "dib_loss_rows_ex": (c_int, [POINTER(LossDesc), c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_float, c_int,
+                                 c_void_p, c_void_p, c_void_p]),
+    "dib_loss_fwd_bwd_ex": (c_int, [c_void_p, POINTER(LossDesc), c_void_p, c_int64, c_void_p, c_int64, c_int, c_float, c_int,
+                                    c_void_p, c_void_p]),
+}
+
+
 def load_library(build_if_missing: bool = True):
     """dlopen libdib_hip.so and attach signatures.  Raises (no fallback) if it cannot be loaded."""
     global _lib
@@ -328,7 +344,7 @@ def _attach(lib):
                            "rebuild it (python -c 'import __graft_entry__ as g; g.build()' / tools/build_variant.sh)")
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_ST.items()) + list(SIGNATURES_MEASURE.items()) \
             + list(SIGNATURES_CIRCUIT.items()) + list(SIGNATURES_PARTITION.items()) + list(SIGNATURES_MI_CHANNEL.items()) + list(SIGNATURES_MI_FEATURES.items()) \
-            + list(SIGNATURES_COMPRESSION.items()) + list(SIGNATURES_OPTIMIZERS.items()):
+            + list(SIGNATURES_COMPRESSION.items()) + list(SIGNATURES_OPTIMIZERS.items()) + list(SIGNATURES_LOSSES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -84,6 +84,7 @@ class HipEngine:
         self._scratch: Optional[torch.Tensor] = None
         self._eval_ws: Dict[int, torch.Tensor] = {}   # batch -> initialised workspace of the evaluation helpers (feature_information)
         self._fused_head: Dict[int, bool] = {}      # loss kind -> dib_output_head_fused_supported
+        self._loss_descs: Dict[tuple, "_lib.LossDesc"] = {}   # losses.LossDescriptor -> its checked dib_loss_desc
         self._infonce_ws: Dict[int, torch.Tensor] = {}   # batch -> workspace of dib_infonce_fwd_bwd
         self.blocks = self._query_blocks()
         self.set_flat_params(self.glorot_uniform(init_seed))
@@ -298,9 +299,20 @@ class HipEngine:
                                             | (_lib.FWD_DEFER_SUMS if defer_sums else 0), _ptr(ws), self._stream()),
               "dib_encoder_bank_fwd")
 
-    def loss(self, loss_kind: str, y: torch.Tensor, row_idx, row0: int, batch: int, inv_global_batch: float,
+    def loss(self, loss_kind, y: torch.Tensor, row_idx, row0: int, batch: int, inv_global_batch: float,
              defer_sums: bool = False) -> None:
+        """loss_kind: a name of LOSS_KINDS (dib_loss_fwd_bwd) or a losses.LossDescriptor (dib_loss_fwd_bwd_ex, the same workspace
+        slots: the backward and the tail follow either unchanged)"""
         ws = self.workspace(batch)
+        if not isinstance(loss_kind, str):
+            desc = self._loss_desc(loss_kind)
+            need = 1 if loss_kind.kind == "sparse_cce" else self.out_dim
+            if y.dim() != 2 or y.shape[1] < need:
+                raise ValueError(f"loss {loss_kind.kind!r} reads {need} label column(s) per row, y is {tuple(y.shape)}")
+            check(self.lib.dib_loss_fwd_bwd_ex(self.layout, ctypes.byref(desc), _ptr(y), y.stride(0), _ptr(row_idx), int(row0), batch,
+                                               float(inv_global_batch), _lib.HEAD_DEFER_SUMS if defer_sums else 0, _ptr(ws),
+                                               self._stream()), "dib_loss_fwd_bwd_ex")
+            return
         check(self.lib.dib_loss_fwd_bwd(self.layout, LOSS_KINDS[loss_kind], _ptr(y), y.stride(0), _ptr(row_idx),
                                         int(row0), batch, float(inv_global_batch), _lib.HEAD_DEFER_SUMS if defer_sums else 0,
                                         _ptr(ws), self._stream()),
@@ -420,7 +432,22 @@ class HipEngine:
                                               _ptr(self.metrics_acc), _ptr(self.workspace(batch)), self._stream()),
               "dib_metrics_accumulate")
 
-    def _head_fused(self, kind: int) -> bool:
+    def _loss_desc(self, d) -> "_lib.LossDesc":
+        """the dib_loss_desc of a losses.LossDescriptor (kept: a captured step holds its address until the launch is recorded);
+        a descriptor the library does not take raises here, before anything is launched"""
+        desc = self._loss_descs.get(d)
+        if desc is None:
+            desc = _lib.LossDesc(int(d.kind_id), int(d.metric_id), float(d.param))
+            if not self.lib.dib_loss_ex_supported(ctypes.byref(desc), self.out_dim):
+                raise ValueError(f"loss descriptor {d!r} is not supported for out_dim {self.out_dim} (include/dib_losses.h)")
+            self._loss_descs[d] = desc
+        return desc
+
+    def _head_fused(self, kind) -> bool:
+        if not isinstance(kind, int):
+            # a descriptor never takes the fused one-unit head: its BCE-from-logits and MSE lines know neither a label smoothing
+            # nor a metric beyond the 0.5-threshold count
+            return False
         fused_head = self._fused_head.get(kind)
         if fused_head is None:
             fused_head = self._fused_head[kind] = bool(self.lib.dib_output_head_fused_supported(self.layout, kind))
@@ -443,7 +470,7 @@ class HipEngine:
             self.optimizer_step(optimizer[1])
             return
         inv = 1.0 / batch if inv_global_batch is None else inv_global_batch
-        kind = LOSS_KINDS[loss_kind]
+        kind = LOSS_KINDS[loss_kind] if isinstance(loss_kind, str) else loss_kind   # (a losses.LossDescriptor: dib_loss_fwd_bwd_ex)
         fused_head = self._head_fused(kind)
         finish = _lib.TAIL_KL | (_lib.TAIL_LOSS_HEAD if fused_head else _lib.TAIL_LOSS) | (_lib.TAIL_METRICS if accumulate else 0)
         if fused_head:
@@ -469,7 +496,7 @@ class HipEngine:
         """validation: noise stays ON and the KL term is included (reference train.py:263-265).  metrics_acc: where the step's
         History sums go (default: the training accumulator; fit passes `metrics_acc_val`)."""
         inv = 1.0 / batch if inv_global_batch is None else inv_global_batch
-        kind = LOSS_KINDS[loss_kind]
+        kind = LOSS_KINDS[loss_kind] if isinstance(loss_kind, str) else loss_kind   # (a losses.LossDescriptor: dib_loss_fwd_bwd_ex)
         fused_head = self._head_fused(kind)
         if fused_head:
             self.encoder_forward(x, row_idx, row0, batch, seed, step, inference=True, defer_sums=True)

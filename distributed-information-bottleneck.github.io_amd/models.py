@@ -374,11 +374,43 @@ class DistributedIBNet:
         """reference train.py:138-142."""
         self.optimizer = _optimizers.get(optimizer)
         self.loss = _losses.get(loss)
+        if isinstance(metrics, str):
+            metrics = [metrics]
         self.metrics_names = list(metrics or [])
-        for m in self.metrics_names:
-            if m not in ("accuracy", "acc"):
-                raise ValueError(f"unsupported metric {m!r} (supported: 'accuracy')")
+        if len(self.metrics_names) > 1:
+            raise ValueError(f"compile(metrics={self.metrics_names!r}): one metric per compile - the step's metric vector has one "
+                             "slot (include/dib_hip.h ws[STEP_OUT][F + 1]); widening it would change the C ABI")
+        self._metric = None   # (History key, DIB_METRIC_* name, square root at the end of the epoch)
+        if self.metrics_names:
+            key, metric, root = _losses.get_metric(self.metrics_names[0])
+            if hasattr(self.loss, "check_metric"):
+                metric = self.loss.check_metric(metric)
+            self._metric = (key, metric, root)
         return self
+
+    def _loss_arg(self):
+        """what the engine's train_step / eval_step take: the kind's name for the reference's own kinds with today's 'accuracy'
+        (dib_loss_fwd_bwd, the fused one-unit head), else the loss's descriptor with the metric (include/dib_losses.h)"""
+        loss, metric = self.loss, (self._metric[1] if getattr(self, "_metric", None) else None)
+        if not hasattr(loss, "descriptor"):
+            return loss.kind   # a foreign object with a `kind`
+        if loss.legacy and metric in (None, loss.resolve_metric("accuracy")):
+            return loss.kind
+        return loss.descriptor(metric)
+
+    def _check_labels(self, loss_arg, y_np: np.ndarray) -> None:
+        """once per fit / evaluate, on the host: the label layout a descriptor's kernel reads (include/dib_losses.h), and for
+        CategoricalCrossentropy(from_logits=True) that every label row sums to 1 (its gradient softmax(z) - y assumes it)"""
+        if isinstance(loss_arg, str):
+            return
+        C = self.output_dimensionality
+        need = 1 if loss_arg.kind == "sparse_cce" else C
+        if y_np.ndim != 2 or y_np.shape[1] != need:
+            raise ValueError(f"loss {loss_arg.kind!r} needs labels of shape [N, {need}], got {tuple(y_np.shape)}")
+        if loss_arg.kind == "cce_logits" and y_np.size:
+            worst = float(np.abs(y_np.astype(np.float64).sum(1) - 1.0).max())
+            if not worst <= 1e-5:
+                raise ValueError(f"CategoricalCrossentropy(from_logits=True): label rows must sum to 1 (worst row is off by {worst:.3g})")
 
     def _dist(self):
         import torch.distributed as dist
@@ -412,14 +444,17 @@ class DistributedIBNet:
         rows = max(acc[F + 2], 1.0)
         logs = {prefix + "loss": acc[F] / rows}
         if self.metrics_names:
-            logs[prefix + "accuracy"] = acc[F + 1] / rows
+            key, _, root = getattr(self, "_metric", None) or ("accuracy", "accuracy", False)
+            # every metric is a sample-weighted mean of per-row values; root_mean_squared_error accumulates the squared errors
+            # and takes the root here, at the end of the epoch (Keras' RootMeanSquaredError.result)
+            logs[prefix + key] = math.sqrt(acc[F + 1] / rows) if root else acc[F + 1] / rows
         for f in range(F):
             logs[f"{prefix}KL{f}"] = acc[f] / max(nsteps, 1)
         logs[prefix + "beta"] = float(self.beta.value())
         return logs
 
     def fit(self, x=None, y=None, batch_size=None, epochs=1, verbose=1, callbacks=None, validation_data=None,
-            shuffle=True, initial_epoch=0, track_information=None, **_):
+            shuffle=True, initial_epoch=0, track_information=None, sample_weight=None, class_weight=None, **_):
         """reference train.py:157-166 `model.fit(x, y, epochs=, shuffle=True, batch_size=, callbacks=,
         verbose=, validation_data=)` -> History.
 
@@ -435,6 +470,9 @@ class DistributedIBNet:
         """
         if self.optimizer is None or self.loss is None:
             raise RuntimeError("call compile(optimizer=..., loss=...) before fit()")
+        if sample_weight is not None or class_weight is not None:
+            raise ValueError("fit(sample_weight=, class_weight=) are not supported: every row of a batch weighs 1 / batch in the "
+                             "loss kernels and in the History accounting")
         eng = self._ensure_engine()
         dist, rank, world = self._dist()
         F = self.number_features
@@ -481,7 +519,10 @@ class DistributedIBNet:
         if track is not None:
             hist.information = {"epochs": [], "beta": [], "bounds": np.zeros((0, F, 2))}
         self.stop_training = False
-        kind = self.loss.kind
+        kind = self._loss_arg()
+        self._check_labels(kind, y_np)
+        if validation_data is not None:
+            self._check_labels(kind, yv_np)
         for cb in cbs:
             if hasattr(cb, "on_train_begin"):
                 cb.on_train_begin()
@@ -681,7 +722,10 @@ class DistributedIBNet:
             raise RuntimeError("call compile() before evaluate()")
         xd = eng.to_device(np.asarray(x, dtype=np.float32))
         y_np = np.asarray(y, dtype=np.float32)
-        yd = eng.to_device(y_np[:, None] if y_np.ndim == 1 else y_np)
+        y_np = y_np[:, None] if y_np.ndim == 1 else y_np
+        yd = eng.to_device(y_np)
+        kind = self._loss_arg()
+        self._check_labels(kind, y_np)
         n, bs = xd.shape[0], int(batch_size or 32)
         eng.read_metrics()
         steps = 0
@@ -690,7 +734,7 @@ class DistributedIBNet:
         while s0 < n:
             b = min(bs, n - s0)
             nb = min(kmerge, (n - s0) // bs) if b == bs else 1
-            eng.eval_step(xd, yd, None, s0, b * nb, self.noise_seed, (1 << 31) - 1, self.loss.kind, inv_global_batch=1.0 / b)
+            eng.eval_step(xd, yd, None, s0, b * nb, self.noise_seed, (1 << 31) - 1, kind, inv_global_batch=1.0 / b)
             steps += nb
             s0 += b * nb
         return self._epoch_logs(eng.read_metrics(), steps, "")

@@ -88,6 +88,10 @@ ORACLE_TESTS = {
     "test_gpu_optimizers.py": {
         "test_every_rule_matches_the_float64_restatement", "test_envelope_of_sizes",
         "test_fit_with_rmsprop_matches_the_float64_oracle_fit", "test_fit_infonce_with_nadam_matches_the_float64_loop_oracle"},
+    "test_gpu_losses.py": {
+        "test_envelope_matches_the_float64_helper", "test_edges_stay_finite_and_gradients_vanish_where_the_contract_says",
+        "test_one_training_step_matches_the_oracle_backward", "test_fit_under_huber_with_mae_matches_the_oracle_fit",
+        "test_fit_on_one_hot_labels_with_smoothing_and_accuracy_matches_the_oracle_fit"},
 }
 # tests that demand the bits (or fp32 summation-order tolerance) of a path the tests above check against an oracle
 EQUIVALENCE_TESTS = {
@@ -130,6 +134,8 @@ EQUIVALENCE_TESTS = {
     "test_gpu_optimizers.py": {
         "test_buckets_then_one_advance_equal_the_whole_buffer_step",
         "test_captured_steps_replay_bit_identically_and_advance_t_and_P"},
+    "test_gpu_losses.py": {
+        "test_bits_do_not_depend_on_the_call_or_the_block", "test_fit_under_graph_replay_has_the_eager_bits_for_a_new_kind"},
 }
 
 
