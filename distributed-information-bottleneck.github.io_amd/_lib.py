@@ -308,6 +308,111 @@ SIGNATURES_LOSSES = {
 }
 
 
+# include/dib_grad_transform.h: gradient clipping over the variables of a flat buffer, learning-rate schedules on the device
+GRAD_TILE = 4096
+CLIP_NONE, CLIP_NORM, CLIP_GLOBAL_NORM = 0, 1, 2
+LR_MAX_BOUNDARIES = 8
+
+
+class GradTile(ctypes.Structure):
+    """dib_grad_tile"""
+    _fields_ = [("start", c_int64), ("count", c_int32), ("segment", c_int32)]
+
+
+class GradTable(ctypes.Structure):
+    """dib_grad_table"""
+    _fields_ = [("n_segments", c_int32), ("reserved", c_int32), ("n_tiles", c_int64), ("seg_tile0", c_void_p),
+                ("tiles_dev", c_void_p), ("seg_tile0_dev", c_void_p)]
+
+
+class LrSchedule(ctypes.Structure):
+    """dib_lr_schedule"""
+    _fields_ = [("kind", c_int32), ("flags", c_int32), ("initial", c_float), ("decay_steps", c_float), ("rate", c_float),
+                ("end", c_float), ("power", c_float), ("alpha", c_float), ("n_boundaries", c_int32), ("reserved", c_int32),
+                ("boundaries", c_int64 * LR_MAX_BOUNDARIES), ("values", c_float * (LR_MAX_BOUNDARIES + 1)), ("reserved2", c_float)]
+
+    @classmethod
+    def from_fields(cls, d: dict) -> "LrSchedule":
+        """from optimizers.Optimizer.lr_schedule() / schedules.LearningRateSchedule.descriptor()"""
+        s = cls()
+        for k in ("kind", "flags"):
+            setattr(s, k, int(d.get(k, 0)))
+        for k in ("initial", "decay_steps", "rate", "end", "power", "alpha"):
+            setattr(s, k, float(d.get(k, 0.0)))
+        b, v = d.get("boundaries", ()), d.get("values", ())
+        if len(b) > LR_MAX_BOUNDARIES or len(v) > LR_MAX_BOUNDARIES + 1:
+            raise ValueError(f"a schedule has at most {LR_MAX_BOUNDARIES} boundaries")
+        s.n_boundaries = len(b)
+        for i, x in enumerate(b):
+            s.boundaries[i] = int(x)
+        for i, x in enumerate(v):
+            s.values[i] = float(x)
+        return s
+
+
+SIGNATURES_GRAD_TRANSFORM = {
+    "dib_grad_table_from_layout": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64), c_int]),
+    "dib_grad_table_tiles": (c_int64, [POINTER(c_int64), POINTER(c_int64), c_int, c_int64, POINTER(GradTile), c_int64,
+                                       POINTER(c_int32)]),
+    "dib_grad_sumsq": (c_int, [POINTER(GradTable), c_int, c_int, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+    "dib_grad_clip_apply": (c_int, [POINTER(GradTable), c_int, c_int, c_void_p, c_float, c_float, c_int, c_float, c_void_p, c_void_p,
+                                    c_int, c_void_p]),
+    "dib_lr_schedule_check": (c_int, [POINTER(LrSchedule)]),
+    "dib_lr_schedule_eval": (c_int, [POINTER(LrSchedule), c_void_p, c_void_p, c_void_p]),
+}
+
+
+class HostGradTable:
+    """The host half of a variable table (include/dib_grad_transform.h): segments, the tile work-list, seg_tile0.  No GPU needed;
+    `upload(device)` makes the dib_grad_table the launches take (engine.py, dense.py)."""
+
+    def __init__(self, offsets, counts, buffer_elems: int):
+        lib = load_library()
+        n = len(offsets)
+        self.offsets, self.counts = [int(o) for o in offsets], [int(c) for c in counts]
+        self.n_segments = n
+        off, cnt = (c_int64 * max(1, n))(*self.offsets), (c_int64 * max(1, n))(*self.counts)
+        nt = int(lib.dib_grad_table_tiles(off, cnt, n, int(buffer_elems), None, 0, None))
+        if nt < 0:
+            raise ValueError(f"dib_grad_table_tiles -> {nt}: the segments are not disjoint pieces of a buffer of {buffer_elems} floats")
+        self.n_tiles = nt
+        self.tiles = (GradTile * max(1, nt))()
+        self.seg_tile0 = (c_int32 * (n + 1))()
+        got = int(lib.dib_grad_table_tiles(off, cnt, n, int(buffer_elems), self.tiles, nt, self.seg_tile0))
+        assert got == nt, (got, nt)
+
+    @classmethod
+    def from_layout(cls, layout, buffer_elems: int) -> "HostGradTable":
+        lib = load_library()
+        n = int(lib.dib_grad_table_from_layout(layout, None, None, 0))
+        if n < 0:
+            raise DibError(f"dib_grad_table_from_layout -> {n}")
+        off, cnt = (c_int64 * n)(), (c_int64 * n)()
+        if int(lib.dib_grad_table_from_layout(layout, off, cnt, n)) != n:
+            raise DibError("dib_grad_table_from_layout refused its own count")
+        return cls(list(off), list(cnt), buffer_elems)
+
+    def segment_range(self, offset: int, count: int):
+        """(first, number) of the segments inside [offset, offset + count) - they must be consecutive in the table and none may
+        straddle an end of the range (a gradient bucket is a union of whole variables)"""
+        inside = [s for s in range(self.n_segments) if offset <= self.offsets[s] and self.offsets[s] + self.counts[s] <= offset + count]
+        cut = [s for s in range(self.n_segments) if s not in inside and self.counts[s] > 0
+               and self.offsets[s] < offset + count and offset < self.offsets[s] + self.counts[s]]
+        if cut or (inside and inside != list(range(inside[0], inside[-1] + 1))):
+            raise ValueError(f"[{offset}, {offset + count}) is not a run of whole variables of the table")
+        return (inside[0], len(inside)) if inside else (0, 0)
+
+    def upload(self, device):
+        """(GradTable, the tensors it points into): tiles and seg_tile0 on `device`"""
+        import numpy as np
+        import torch
+        tiles = np.frombuffer(self.tiles, dtype=np.uint8, count=16 * self.n_tiles).copy()
+        tiles_dev = torch.from_numpy(tiles if self.n_tiles else np.zeros(16, np.uint8)).to(device)
+        seg_dev = torch.from_numpy(np.frombuffer(self.seg_tile0, dtype=np.int32).copy()).to(device)
+        t = GradTable(self.n_segments, 0, self.n_tiles, ctypes.cast(self.seg_tile0, c_void_p), tiles_dev.data_ptr(), seg_dev.data_ptr())
+        return t, (tiles_dev, seg_dev, self)
+
+
 def load_library(build_if_missing: bool = True):
     """dlopen libdib_hip.so and attach signatures.  Raises (no fallback) if it cannot be loaded."""
     global _lib
@@ -344,7 +449,8 @@ def _attach(lib):
                            "rebuild it (python -c 'import __graft_entry__ as g; g.build()' / tools/build_variant.sh)")
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_ST.items()) + list(SIGNATURES_MEASURE.items()) \
             + list(SIGNATURES_CIRCUIT.items()) + list(SIGNATURES_PARTITION.items()) + list(SIGNATURES_MI_CHANNEL.items()) + list(SIGNATURES_MI_FEATURES.items()) \
-            + list(SIGNATURES_COMPRESSION.items()) + list(SIGNATURES_OPTIMIZERS.items()) + list(SIGNATURES_LOSSES.items()):
+            + list(SIGNATURES_COMPRESSION.items()) + list(SIGNATURES_OPTIMIZERS.items()) + list(SIGNATURES_LOSSES.items()) \
+            + list(SIGNATURES_GRAD_TRANSFORM.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -260,23 +260,50 @@ class DenseStack:
                                      self.n_params, _ptr(self.lr_dev), _ptr(self.t_dev), beta1, beta2, eps, 1.0,
                                      self.eng._stream()), "dib_adam_step")
 
-    def optimizer_step(self, opt, lr: Optional[float] = None) -> None:
+    def reduce_pending(self) -> None:
+        """self.grads <- the fixed-order sum of the slabs a backward(reduce=False) left (nothing when there are none)"""
+        pl = self._unreduced
+        if pl is not None:
+            check(self.lib.dib_reduce_splits(_ptr(pl["slabs"]), self.n_params, pl["nsplit"], self.n_params, _ptr(self.grads),
+                                             self.eng._stream()), "dib_reduce_splits")
+            self._unreduced = None
+
+    def grad_transform(self):
+        """gradient clipping on this stack's buffer (include/dib_grad_transform.h): one variable per Dense kernel and bias, in
+        layer order; the 4-float alignment gaps after them belong to none"""
+        if getattr(self, "_grad_transform", None) is None:
+            from . import _lib
+            from .grad_transform import GradTransform
+            offs, cnts = [], []
+            for (i, o), w, b in zip(self.dims, self.w_off, self.b_off):
+                offs += [w, b]
+                cnts += [i * o, o]
+            self._grad_transform = GradTransform(self.lib, _lib.HostGradTable(offs, cnts, self.n_params), self.grads, self.eng._stream)
+        return self._grad_transform
+
+    def apply_lr(self, descriptor: dict) -> None:
+        """lr_dev <- the schedule at this stack's step count, on the device (dib_lr_schedule_eval)"""
+        from .grad_transform import eval_lr
+        eval_lr(self.lib, descriptor, self.t_dev, self.lr_dev, self.eng._stream())
+
+    def optimizer_step(self, opt, lr: Optional[float] = None, transform: bool = True) -> None:
         """One update by any optimizers.Optimizer (the custom loop steps both networks with one Keras optimizer, reference
         train.py:196,219).  Slabs a backward(reduce=False) left are summed first.  Adam: adam_step, its launches and bits; plain
         SGD: dib_sgd_step; every other rule: dib_optimizer_step + dib_optimizer_advance (include/dib_optimizers.h) on this
         stack's own state - adam_m, adam_v, a third buffer allocated when a rule first needs it, its step count and Nadam's P.
-        A change of rule re-initialises that state."""
+        A change of rule re-initialises that state.  The optimizer's clip arguments transform the final gradient first - a
+        clipped step cannot use the fused sum-and-Adam launch (transform=False: the caller already did, with a norm over both
+        networks)."""
         if lr is not None:
             self.lr_dev.fill_(float(lr))
+        if transform and opt.clip() is not None:
+            self.reduce_pending()
+            self.grad_transform().transform(opt.clip())
         if opt.native and opt.name == "adam":
             self.adam_step(None, opt.beta_1, opt.beta_2, opt.epsilon, fused_reduce=self._unreduced is not None)
             return
         st = self.eng._stream()
-        pl = self._unreduced
-        if pl is not None:
-            check(self.lib.dib_reduce_splits(_ptr(pl["slabs"]), self.n_params, pl["nsplit"], self.n_params, _ptr(self.grads), st),
-                  "dib_reduce_splits")
-            self._unreduced = None
+        self.reduce_pending()
         if opt.native:
             check(self.lib.dib_sgd_step(_ptr(self.params), _ptr(self.grads), self.n_params, _ptr(self.lr_dev), 1.0, st), "dib_sgd_step")
             return

@@ -233,10 +233,15 @@ class HipEngine:
         check(self.lib.dib_optimizer_advance(opt.kind, byref(self._opt_hyper(opt)), _ptr(self.t_dev), _ptr(self._opt_scalar(opt)),
                                              self._stream()), "dib_optimizer_advance")
 
-    def optimizer_step(self, opt, grad_scale: float = 1.0) -> None:
+    def optimizer_step(self, opt, grad_scale: float = 1.0, transform: bool = True) -> None:
         """One update of the whole flat buffer from self.grads by any optimizers.Optimizer: Adam and momentum-free SGD through
-        adam_step / sgd_step (their launches and bits), every other rule through dib_optimizer_step + dib_optimizer_advance."""
+        adam_step / sgd_step (their launches and bits), every other rule through dib_optimizer_step + dib_optimizer_advance.
+        The optimizer's clip arguments transform self.grads first (transform=False: the caller already did, e.g. with a norm
+        over several buffers)."""
         self.set_optimizer(opt)
+        if transform and opt.clip() is not None:   # the rule then reads the transformed gradient, grad_scale folded in
+            self.transform_gradients(opt, grad_scale)
+            grad_scale = 1.0
         if opt.native:
             if opt.name == "adam":
                 self.adam_step(opt.beta_1, opt.beta_2, opt.epsilon, grad_scale)
@@ -245,6 +250,44 @@ class HipEngine:
             return
         self.optimizer_step_range(opt, 0, self.n_params, grad_scale)
         self.optimizer_advance(opt)
+
+    # ---- gradient clipping and learning-rate schedules (include/dib_grad_transform.h) ------------------------------------------
+    def grad_transform(self) -> "GradTransform":
+        """the variable table of the layout on the device, the tile partials and the ss array: made once per engine"""
+        if getattr(self, "_grad_transform", None) is None:
+            from .grad_transform import GradTransform
+            host = _lib.HostGradTable.from_layout(self.layout, self.grads.numel())
+            self._grad_transform = GradTransform(self.lib, host, self.grads, self._stream)
+        return self._grad_transform
+
+    def transform_gradients(self, opt, grad_scale: float = 1.0) -> None:
+        """self.grads <- what the rule of `opt` sees (clipvalue, then clipnorm or global_clipnorm, grad_scale folded in), over the
+        whole buffer: 1 launch for clipvalue alone, 3 with a norm.  Nothing for an optimizer without clip arguments."""
+        clip = opt.clip()
+        if clip is not None:
+            self.grad_transform().transform(clip, None, grad_scale)
+
+    def part_segments(self, part: int):
+        """(first, number) of the variable-table segments of gradient bucket `part`: a bucket is a run of whole variables"""
+        cache = self.__dict__.setdefault("_part_segments", {})
+        if part not in cache:
+            cache[part] = self.grad_transform().host.segment_range(*self.part_range(part))
+        return cache[part]
+
+    def apply_lr(self, opt) -> None:
+        """the learning rate of the next step: a constant through set_lr (nothing when unchanged); `decay` or a schedule through
+        the one-thread kernel that reads the device step count, which then owns lr_dev"""
+        d = opt.lr_schedule()
+        if d is None:
+            self.set_lr(opt.learning_rate)
+        else:
+            self.apply_lr_descriptor(d)
+
+    def apply_lr_descriptor(self, descriptor: dict) -> None:
+        """lr_dev <- the schedule (fields of dib_lr_schedule) at the device step count; the host cache of set_lr is void after it"""
+        from .grad_transform import eval_lr
+        eval_lr(self.lib, descriptor, self.t_dev, self.lr_dev, self._stream())
+        self.invalidate_lr_cache()
 
     def set_beta(self, v: float) -> None:
         self.beta_dev.fill_(float(v))
@@ -341,13 +384,41 @@ class HipEngine:
     def optimizer_step_part(self, batch: int, part: int, optimizer, bump: bool) -> None:
         """the optimizer on ONE gradient bucket (after its all-reduce): the data-parallel fit steps buckets 1 and 2 while
         bucket 3 is still on the wire; the launch with bump=True (the last) advances Adam's step count."""
-        if optimizer[0] == "opt":   # ("opt", Optimizer): a rule of include/dib_optimizers.h - a range launch, the advance with the last
-            off, cnt = self.part_range(part)
-            self.optimizer_step_range(optimizer[1], off, cnt)
-            if bump:
-                self.optimizer_advance(optimizer[1])
+        if optimizer[0] == "opt":   # ("opt", Optimizer): a rule of include/dib_optimizers.h, or any rule behind a gradient transform
+            opt = optimizer[1]
+            clip = opt.clip()
+            if clip is not None and clip[1] == _lib.CLIP_GLOBAL_NORM:
+                # the norm is over every bucket: this one's sums of squares now, while later buckets are on the wire; all buckets
+                # are transformed (one launch: together they are the whole table) and stepped after the last has landed
+                gt = self.grad_transform()
+                gt.sumsq(clip, self.part_segments(part))
+                held = self.__dict__.setdefault("_held_parts", [])
+                held.append(part)
+                if not bump:
+                    return
+                assert sum(self.part_segments(p)[1] for p in held) == gt.n_segments, "the buckets of a step cover every variable"
+                gt.apply(clip)
+                parts = list(held)
+                held.clear()
+                for k, p in enumerate(parts):
+                    self._rule_on_part(batch, p, opt, bump=k == len(parts) - 1)
+                return
+            if clip is not None:   # clipvalue / clipnorm are per variable: the bucket is transformed as soon as it has landed
+                self.grad_transform().transform(clip, self.part_segments(part))
+            self._rule_on_part(batch, part, opt, bump)
             return
         self.step_tail(batch, part, _lib.TAIL_BUMP if (bump and optimizer[0] == "adam") else 0, optimizer=optimizer)
+
+    def _rule_on_part(self, batch: int, part: int, opt, bump: bool) -> None:
+        """the rule of `opt` on one bucket whose gradient is final in self.grads; bump: the step's last launch of the rule"""
+        if opt.native:   # Adam / momentum-free SGD: the tail's update on the bucket (dib_adam_step's expressions), no finalize
+            tup = ("adam", opt.beta_1, opt.beta_2, opt.epsilon) if opt.name == "adam" else ("sgd",)
+            self.step_tail(batch, part, _lib.TAIL_BUMP if (bump and opt.name == "adam") else 0, optimizer=tup)
+            return
+        off, cnt = self.part_range(part)
+        self.optimizer_step_range(opt, off, cnt)
+        if bump:
+            self.optimizer_advance(opt)
 
     def part_range(self, part: int):
         """(offset, count) of gradient bucket `part` in the flat buffers (include/dib_hip.h): 0 = encoder bank,

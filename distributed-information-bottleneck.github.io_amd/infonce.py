@@ -232,12 +232,44 @@ def fit_infonce(model, x_train, y_train, x_valid, y_valid, *, batch_size: int, n
     # the learning rate is constant over this loop (train.py:128-129): one device scalar per network, set once
     eng.set_lr(learning_rate)
     yenc.set_lr(learning_rate)
+    # ... unless the optimizer carries `decay` or a schedule: then each network's rate is evaluated on the device from its own step
+    # count ahead of every training step (the two counts advance together); `decay` starts from this loop's learning_rate
+    lr_desc = None if opt is None else opt.lr_schedule()
+    if lr_desc is not None and not isinstance(opt.learning_rate, _optimizers._schedules.LearningRateSchedule):
+        lr_desc = dict(lr_desc, initial=float(learning_rate))
+    clip = None if opt is None else opt.clip()
+    if clip is not None and clip[1] == _optimizers.CLIP_GLOBAL_NORM:
+        # one gradient list over both networks (train.py:196-219): their sums of squares share one array, the norm is over it
+        ge, gy = eng.grad_transform(), yenc.grad_transform()
+        ss_all = torch.zeros(ge.n_segments + gy.n_segments, dtype=torch.float64, device=eng.device)
+        ge.bind_ss(ss_all, 0)
+        gy.bind_ss(ss_all, ge.n_segments)
+
+    def step_both():
+        """both networks' update by `opt` from their final gradients, the clip arguments applied first"""
+        if clip is None:
+            eng.optimizer_step(opt)
+            yenc.optimizer_step(opt)
+            return
+        yenc.reduce_pending()   # clipping reads the Y encoder's final gradient: the fixed-order sum of its partials
+        ge, gy = eng.grad_transform(), yenc.grad_transform()
+        if clip[1] == _optimizers.CLIP_GLOBAL_NORM:
+            ge.sumsq(clip)
+            gy.sumsq(clip)
+            ge.apply(clip)
+            gy.apply(clip)
+        else:
+            ge.transform(clip)
+            gy.transform(clip)
+        eng.optimizer_step(opt, transform=False)
+        yenc.optimizer_step(opt, transform=False)
 
     from . import _lib
     adam = ("adam", 0.9, 0.999, 1e-7)                             # tf.keras.optimizers.Adam defaults (train.py:128-129)
     if opt is not None and opt.native and opt.name == "adam":
         adam = ("adam", opt.beta_1, opt.beta_2, opt.epsilon)
-    tail_opt = adam if opt is None or (opt.native and opt.name == "adam") else None   # Adam rides in the step's tail launch
+    # Adam rides in the step's tail launch - unless its gradient is clipped first
+    tail_opt = adam if opt is None or (opt.native and opt.name == "adam" and clip is None) else None
     slots = _LossSlots(eng.device, eng.metrics_acc.dtype)
     # single process: the per-feature KL of every step is accumulated on the device by the step's LAST launch (metrics_acc[f] +=
     # KL_f sum / B, dib_step_tail) - training and validation into accumulators of THIS loop, read once per epoch boundary.
@@ -260,6 +292,9 @@ def fit_infonce(model, x_train, y_train, x_valid, y_valid, *, batch_size: int, n
                                        out_gx=eng.g_pred(B) if training else None,
                                        out_gy=yenc.output_grad_buffer() if training else None, loss_out=slots.next())
             if training:
+                if lr_desc is not None:
+                    eng.apply_lr_descriptor(lr_desc)
+                    yenc.apply_lr(lr_desc)
                 compb = yenc.companion_backward(gy) if comp is not None else None
                 eng.backward_from_pred_grad(gx, idx, 0, B, model.noise_seed, step, inv_global_batch=1.0 / batch_size,
                                             finish_flags=_lib.TAIL_KL | _lib.TAIL_METRICS, optimizer=tail_opt, metrics_acc=kl_acc["kl"],
@@ -268,8 +303,7 @@ def fit_infonce(model, x_train, y_train, x_valid, y_valid, *, batch_size: int, n
                 if tail_opt is not None:
                     yenc.adam_step(None, *adam[1:], fused_reduce=True)   # one Keras Adam over all variables (train.py:196,219)
                 else:                                              # any other rule: the same optimizer, the same t, both networks
-                    eng.optimizer_step(opt)
-                    yenc.optimizer_step(opt)
+                    step_both()
             else:
                 eng.step_tail(B, -1, _lib.TAIL_KL | _lib.TAIL_METRICS, 1.0 / batch_size, metrics_acc=kl_acc["kl_validation"])
             return loss, None
@@ -286,12 +320,14 @@ def fit_infonce(model, x_train, y_train, x_valid, y_valid, *, batch_size: int, n
             yenc.backward(gy)
             dist.all_reduce(eng.grads)
             dist.all_reduce(yenc.grads)
+            if lr_desc is not None:
+                eng.apply_lr_descriptor(lr_desc)
+                yenc.apply_lr(lr_desc)
             if opt is None:
                 eng.adam_step()                                    # one Keras Adam over all variables (train.py:196,219)
                 yenc.adam_step()
             else:
-                eng.optimizer_step(opt)
-                yenc.optimizer_step(opt)
+                step_both()
         return loss, kl
 
     def epoch_mean(name, values):
@@ -315,5 +351,8 @@ def fit_infonce(model, x_train, y_train, x_valid, y_valid, *, batch_size: int, n
     finally:   # also when a step or the caller's epoch_callback raises: no worker thread / pending draw left behind
         train_idx["next"].cancel()
         pool.shutdown(wait=True, cancel_futures=True)
+        if clip is not None and clip[1] == _optimizers.CLIP_GLOBAL_NORM:   # the engine's norm is its own again (a later model.fit)
+            eng.grad_transform().unbind_ss()
+            yenc.grad_transform().unbind_ss()
     out['kl_total'], out['kl_total_validation'] = out['kl'].sum(-1), out['kl_validation'].sum(-1)
     return out

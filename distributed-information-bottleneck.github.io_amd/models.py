@@ -420,16 +420,26 @@ class DistributedIBNet:
 
     def _optimizer_tuple(self):
         """what HipEngine.train_step / optimizer_step_part take: Adam and momentum-free SGD ride in the step tail; every other
-        rule (optimizers.Optimizer.native is False) is ("opt", optimizer): dib_optimizer_step + dib_optimizer_advance"""
+        rule (optimizers.Optimizer.native is False) and every rule behind a gradient transform (clipvalue, clipnorm,
+        global_clipnorm: the transform launches run between the tail and the update) is ("opt", optimizer)"""
         opt = self.optimizer
-        if not opt.native:
+        if not opt.native or opt.clip() is not None:
             return ("opt", opt)
         return ("adam", opt.beta_1, opt.beta_2, opt.epsilon) if opt.name == "adam" else ("sgd",)
 
+    def _set_lr(self, eng):
+        """the learning rate of the next step on the device: a constant is set from the host (free when unchanged); `decay` or a
+        schedule is evaluated on the device from the step count (HipEngine.apply_lr, include/dib_grad_transform.h)"""
+        opt = self.optimizer
+        if opt.lr_schedule() is None:
+            eng.set_lr(opt.learning_rate)
+        else:
+            eng.apply_lr(opt)
+
     def _optimizer_step(self, eng):
         opt = self.optimizer
-        eng.set_lr(opt.learning_rate)
-        if not opt.native:
+        self._set_lr(eng)
+        if not opt.native or opt.clip() is not None:
             eng.optimizer_step(opt)
         elif opt.name == "adam":
             eng.adam_step(opt.beta_1, opt.beta_2, opt.epsilon)
@@ -544,14 +554,17 @@ class DistributedIBNet:
             eng.set_optimizer(self.optimizer)   # a change of rule re-initialises the optimizer state; the same rule: nothing
         elif not self.optimizer.native:
             raise ValueError(f"optimizer {self.optimizer.name!r} needs the HIP engine (include/dib_optimizers.h)")
-        # (the rules of include/dib_optimizers.h always run eagerly: their step is not part of capture_step_graph)
+        if not hasattr(eng, "apply_lr") and (self.optimizer.clip() is not None or self.optimizer.lr_schedule() is not None):
+            raise ValueError("gradient clipping, decay and learning-rate schedules need the HIP engine (include/dib_grad_transform.h)")
+        # (the rules of include/dib_optimizers.h and every step behind a gradient transform always run eagerly: their step is not
+        # part of capture_step_graph; a schedule alone keeps the captured step - its one-thread launch goes ahead of each replay)
         use_graphs = (dist is None and hasattr(eng, "capture_step_graph") and bs <= 8192 and n_full * epochs >= 64
-                      and self.optimizer.native
+                      and self.optimizer.native and self.optimizer.clip() is None
                       and os.environ.get("DIB_ENABLE_GRAPHS", "0") == "1")
         graphs = {}
         if use_graphs:
             eng.enable_step_counter(self._step)
-            eng.set_lr(self.optimizer.learning_rate)
+            self._set_lr(eng)
             opt_args = ((self.optimizer.beta_1, self.optimizer.beta_2, self.optimizer.epsilon)
                         if self.optimizer.name == "adam" else ())
             graphs["train"] = eng.capture_step_graph(xd, yd, bs, kind, 1.0 / bs, self.noise_seed, True,
@@ -578,7 +591,7 @@ class DistributedIBNet:
                     gb = min(bs, n - s0)  # last partial batch is kept (Keras)
                     if use_graphs and gb == bs:
                         g, stage = graphs["train"]
-                        eng.set_lr(self.optimizer.learning_rate)
+                        self._set_lr(eng)
                         stage.copy_(order_dev[s0: s0 + bs])
                         g.replay()  # fwd + loss + bwd + optimizer + metrics + step-counter bump
                         self._step += 1
@@ -605,7 +618,7 @@ class DistributedIBNet:
                     if dist is None and getattr(eng, "fused_optimizer_tail", False):
                         # one process: the step's LAST launch reduces the gradient partials, sums the KL / loss partials,
                         # accumulates the History metrics and applies the optimizer (csrc/dib_tail.h)
-                        eng.set_lr(self.optimizer.learning_rate)
+                        self._set_lr(eng)
                         eng.train_step(xd, yd, order_dev[s0: s0 + gb], 0, gb, self.noise_seed, self._step, kind,
                                        inv_global_batch=1.0 / gb, optimizer=self._optimizer_tuple())
                         self._step += 1
@@ -629,7 +642,7 @@ class DistributedIBNet:
                             # each bucket is stepped as soon as ITS all-reduce has landed: buckets 1 (and 2) are updated on
                             # the compute stream while the last bucket is still on the wire; every launch reads the same
                             # Adam step count, the last one advances it
-                            eng.set_lr(self.optimizer.learning_rate)
+                            self._set_lr(eng)
                             parts = (1, 2, 3) if nb == 3 else (1, 0)
                             for k, (w, part) in enumerate(zip(pending, parts)):
                                 w.wait()

@@ -1,22 +1,38 @@
 """Keras-shaped optimizer objects (reference train.py:128-129: tf.keras.optimizers.get(name); optimizer.learning_rate = 3e-4).
 The update itself is a fused flat-buffer HIP kernel: dib_adam_kernel / dib_sgd_kernel (and the step tail) for Adam and
 momentum-free SGD, the dib_opt_kernel family (csrc/dib_optimizers.h, include/dib_optimizers.h) for every other rule.  The rules
-are Keras optimizer_v2's (TF 2.x before 2.11)."""
+are Keras optimizer_v2's (TF 2.x before 2.11).  So are clipvalue, clipnorm, global_clipnorm (the gradient the rule
+sees, include/dib_grad_transform.h), the legacy `decay` and a schedules.LearningRateSchedule as `learning_rate` (the rate of a step,
+evaluated on the device from the step count).  The four clip / decay settings are ATTRIBUTES, as optimizer_v2 has them too -
+`opt = Adam(3e-4); opt.clipnorm = 1.0`, `opt.configure(global_clipnorm=1.0)`, `optimizers.get("adam", clipnorm=1.0)`,
+`optimizers.build(Adam, 3e-4, clipnorm=1.0)` - and NOT constructor keywords: the constructors keep refusing every keyword that
+would change the update (tests/test_optimizers_host.py pins that), with a message that names the attribute route.  A change of
+those settings is not a change of rule: it does not reset the optimizer state."""
 from __future__ import annotations
+
+from . import schedules as _schedules
 
 # include/dib_optimizers.h DIB_OPT_*
 OPT_SGD_MOMENTUM, OPT_RMSPROP, OPT_ADAGRAD, OPT_ADADELTA, OPT_ADAMAX, OPT_NADAM, OPT_AMSGRAD = range(1, 8)
 
 SUPPORTED = ("adadelta", "adagrad", "adam", "adamax", "nadam", "rmsprop", "sgd")
-# Keras arguments that change the update and that no kernel here applies: refused, never dropped
-UNSUPPORTED_ARGUMENTS = ("clipnorm", "clipvalue", "global_clipnorm", "decay", "weight_decay", "use_ema")
+# Keras >= 2.11 arguments (optimizer_v2 never had them) that no kernel here applies: refused, never dropped
+UNSUPPORTED_ARGUMENTS = ("weight_decay", "use_ema")
+# optimizer_v2's arguments that change the gradient or the learning rate before the rule sees them (include/dib_grad_transform.h)
+TRANSFORM_ARGUMENTS = ("clipnorm", "clipvalue", "global_clipnorm", "decay")
+# include/dib_grad_transform.h DIB_CLIP_*
+CLIP_NONE, CLIP_NORM, CLIP_GLOBAL_NORM = 0, 1, 2
 
 
 def _reject(cls_name: str, kwargs: dict) -> None:
     for k in kwargs:
         if k in UNSUPPORTED_ARGUMENTS:
-            raise ValueError(f"{cls_name}: argument {k!r} is not supported (gradient clipping, decay and EMA are not "
-                             f"implemented; supported optimizers: {', '.join(SUPPORTED)})")
+            raise ValueError(f"{cls_name}: argument {k!r} is not supported (weight_decay and use_ema belong to the Keras >= 2.11 "
+                             f"optimizers, not to optimizer_v2 whose rules these are; supported optimizers: {', '.join(SUPPORTED)})")
+        if k in TRANSFORM_ARGUMENTS:
+            raise ValueError(f"{cls_name}: {k!r} is not a constructor argument here: set it on the object (optimizer.{k} = value, or "
+                             f"optimizer.configure({k}=value)) or pass it to optimizers.get(name, {k}=value) / "
+                             f"optimizers.build({cls_name}, ..., {k}=value) (supported optimizers: {', '.join(SUPPORTED)})")
         if k != "name":   # (Keras' cosmetic `name` changes nothing)
             raise ValueError(f"{cls_name}: unknown argument {k!r} (supported optimizers: {', '.join(SUPPORTED)})")
 
@@ -25,8 +41,85 @@ class Optimizer:
     name = "optimizer"
     kind = 0   # DIB_OPT_* of the dib_optimizer_* entries; 0: the rule has launches of its own (Adam, momentum-free SGD)
 
-    def __init__(self, learning_rate: float):
-        self.learning_rate = float(learning_rate)
+    def __init__(self, learning_rate):
+        self._clip = dict(clipnorm=None, clipvalue=None, global_clipnorm=None)
+        self._decay = 0.0
+        self.learning_rate = learning_rate
+
+    # ---- what happens to the gradient and the learning rate before the rule (include/dib_grad_transform.h) ----------------------
+    def _set_threshold(self, key: str, value) -> None:
+        """a clip threshold: None, or a finite number > 0; clipnorm and global_clipnorm exclude each other"""
+        cls = type(self).__name__
+        if value is not None:
+            v = float(value)
+            if not (v > 0.0 and v < float("inf")):
+                raise ValueError(f"{cls}: {key} must be a positive number, got {value!r}")
+            other = {"clipnorm": "global_clipnorm", "global_clipnorm": "clipnorm"}.get(key)
+            if other is not None and self._clip[other] is not None:
+                raise ValueError(f"{cls}: Cannot accept both `clipnorm` and `global_clipnorm`, got {key}={value!r} with "
+                                 f"{other}={self._clip[other]!r}")
+            value = v
+        self._clip[key] = value
+
+    clipnorm = property(lambda self: self._clip["clipnorm"], lambda self, v: self._set_threshold("clipnorm", v),
+                        doc="per variable: g = (g * c) / max(||g||, c); None = off")
+    clipvalue = property(lambda self: self._clip["clipvalue"], lambda self, v: self._set_threshold("clipvalue", v),
+                         doc="per element: g = min(max(g, -c), c); None = off")
+    global_clipnorm = property(lambda self: self._clip["global_clipnorm"], lambda self, v: self._set_threshold("global_clipnorm", v),
+                               doc="over all variables: g = g * c * min(1 / N, 1 / c); None = off")
+
+    @property
+    def decay(self) -> float:
+        """the legacy `decay`: lr_t = lr / (1 + decay * iterations); 0 = off"""
+        return self._decay
+
+    @decay.setter
+    def decay(self, value) -> None:
+        v = float(value or 0.0)
+        if not (0.0 <= v < float("inf")):
+            raise ValueError(f"{type(self).__name__}: decay must be non-negative, got {value!r}")
+        if v > 0.0 and self._schedule is not None:
+            raise ValueError(f"{type(self).__name__}: a LearningRateSchedule and the legacy `decay` cannot be combined")
+        self._decay = v
+
+    def configure(self, **settings) -> "Optimizer":
+        """assign any of clipnorm, clipvalue, global_clipnorm, decay; returns self"""
+        for k, v in settings.items():
+            if k not in TRANSFORM_ARGUMENTS:
+                raise ValueError(f"{type(self).__name__}.configure: unknown setting {k!r} (settings: {', '.join(TRANSFORM_ARGUMENTS)})")
+            setattr(self, k, v)
+        return self
+
+    @property
+    def learning_rate(self):
+        """a float, or the schedules.LearningRateSchedule given; assigning a float replaces a schedule (reference train.py:129)"""
+        return self._schedule if self._schedule is not None else self._lr
+
+    @learning_rate.setter
+    def learning_rate(self, value):
+        if isinstance(value, _schedules.LearningRateSchedule):
+            if self._decay > 0.0:
+                raise ValueError(f"{type(self).__name__}: a LearningRateSchedule and the legacy `decay` cannot be combined")
+            self._schedule, self._lr = value, float(value(0))
+        else:
+            self._schedule, self._lr = None, float(value)
+
+    def lr_schedule(self):
+        """None for a constant learning rate (HipEngine.set_lr), else the fields of dib_lr_schedule: the rate is evaluated on the
+        device from the step count by dib_lr_schedule_eval"""
+        if self._schedule is not None:
+            return self._schedule.descriptor()
+        if self._decay > 0.0:
+            return _schedules.inverse_decay_descriptor(self._lr, self._decay)
+        return None
+
+    def clip(self):
+        """None, or (clipvalue or 0.0, DIB_CLIP_* mode, norm threshold): the transform of include/dib_grad_transform.h that runs on
+        the aggregated gradient before the rule.  An optimizer with one never rides in the step tail."""
+        if self.clipnorm is None and self.global_clipnorm is None and self.clipvalue is None:
+            return None
+        mode = CLIP_NORM if self.clipnorm is not None else CLIP_GLOBAL_NORM if self.global_clipnorm is not None else CLIP_NONE
+        return (self.clipvalue or 0.0, mode, self.clipnorm or self.global_clipnorm or 0.0)
 
     @property
     def native(self) -> bool:
@@ -171,12 +264,21 @@ _BY_NAME = {"adam": Adam, "sgd": SGD, "rmsprop": RMSprop, "adagrad": Adagrad, "a
             "nadam": Nadam}
 
 
-def get(identifier) -> Optimizer:
-    """tf.keras.optimizers.get: an Optimizer instance, or one of the names (any letter case) with the Keras defaults."""
+def build(cls, *args, **kwargs) -> Optimizer:
+    """cls(*args, **rule keywords) with the clip / decay keywords among `kwargs` assigned afterwards (Optimizer.configure)"""
+    settings = {k: kwargs.pop(k) for k in TRANSFORM_ARGUMENTS if k in kwargs}
+    return cls(*args, **kwargs).configure(**settings)
+
+
+def get(identifier, **kwargs) -> Optimizer:
+    """tf.keras.optimizers.get: an Optimizer instance, or one of the names (any letter case) with the Keras defaults.  Keyword
+    arguments (not Keras': the training script's clip / decay flags) go with a name: `build` of the named class."""
     if isinstance(identifier, Optimizer):
+        if kwargs:
+            raise ValueError("optimizers.get: keyword arguments go with a name, not with an Optimizer instance")
         return identifier
     if isinstance(identifier, str):
         cls = _BY_NAME.get(identifier.lower())
         if cls is not None:
-            return cls()
+            return build(cls, **kwargs)
     raise ValueError(f"unsupported optimizer {identifier!r} (supported: {', '.join(repr(n) for n in SUPPORTED)})")

@@ -42,6 +42,12 @@ def get_args(argv=None):
     p.add_argument('--feature_embedding_dimension', type=int, default=32)
     p.add_argument('--optimizer', type=str, default='adam',
                    help='a Keras optimizer name: adam, sgd, rmsprop, adagrad, adadelta, adamax, nadam (Keras defaults)')
+    p.add_argument('--clipnorm', type=float, default=None, help='clip every variable\'s gradient to this L2 norm (Keras clipnorm)')
+    p.add_argument('--clipvalue', type=float, default=None, help='clip every gradient element to [-v, v] (Keras clipvalue)')
+    p.add_argument('--global_clipnorm', type=float, default=None,
+                   help='clip the gradient of all variables to this joint L2 norm (Keras global_clipnorm)')
+    p.add_argument('--learning_rate_decay', type=float, default=None,
+                   help='legacy Keras `decay`: learning_rate / (1 + decay * iterations)')
     p.add_argument('--save_compression_matrices_frequency', type=int, default=0)
     p.add_argument('--compression_matrices_one_launch', type=_bool, default=False,
                    help='evaluate the compression matrices of all features from one encoder-bank forward and one launch per '
@@ -138,7 +144,10 @@ def main(argv=None):
             args.save_compression_matrices_frequency, dataset_dict['x_valid'],
             dataset_dict.get('x_valid_raw', dataset_dict['x_valid']), args.artifact_outdir,
             one_launch=args.compression_matrices_one_launch)
-    optimizer = optimizers.get(args.optimizer)  # any Keras name; both branches train with it (train.py:128-129, 196, 219)
+    # any Keras name; both branches train with it (train.py:128-129, 196, 219), behind the clip / decay arguments that were given
+    transforms = dict(clipnorm=args.clipnorm, clipvalue=args.clipvalue, global_clipnorm=args.global_clipnorm,
+                      decay=args.learning_rate_decay)
+    optimizer = optimizers.get(args.optimizer, **{k: v for k, v in transforms.items() if v is not None})
     optimizer.learning_rate = args.learning_rate
     if args.infonce_loss:  # ---- custom training loop, reference train.py:180-289 ----
         from . import infonce

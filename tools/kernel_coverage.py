@@ -4,6 +4,8 @@
       DIB_COVERAGE_LOG=/tmp/cov/tests.tsv rocprofv3 --kernel-trace --marker-trace -M -f csv -d /tmp/cov/trace -- \
           python -m pytest tests -m gpu -q
       python tools/kernel_coverage.py build /tmp/cov/trace /tmp/cov/tests.tsv gpurun_out/r06_suite_kernel_coverage.txt
+  a suite too long for one visit is traced in parts (disjoint sets of test files, `build` once per part, anywhere afterwards):
+      python tools/kernel_coverage.py merge profiles/r06_suite_kernel_coverage.txt PART_A.txt PART_B.txt
   anywhere (tests/test_kernel_coverage.py, no GPU):
       python tools/kernel_coverage.py check profiles/r06_suite_kernel_coverage.txt
 
@@ -88,6 +90,12 @@ ORACLE_TESTS = {
     "test_gpu_optimizers.py": {
         "test_every_rule_matches_the_float64_restatement", "test_envelope_of_sizes",
         "test_fit_with_rmsprop_matches_the_float64_oracle_fit", "test_fit_infonce_with_nadam_matches_the_float64_loop_oracle"},
+    "test_gpu_grad_transforms.py": {
+        "test_envelope_matches_the_float64_restatement", "test_real_layouts",
+        "test_two_buffers_sharing_one_ss_array_take_the_norm_of_their_union", "test_learning_rate_on_the_device",
+        "test_eight_steps_with_the_rules_match_the_composed_restatement",
+        "test_fit_with_global_clipnorm_and_exponential_decay_matches_the_float64_oracle_fit",
+        "test_fit_infonce_with_clipnorm_matches_the_float64_loop_oracle"},
     "test_gpu_losses.py": {
         "test_envelope_matches_the_float64_helper", "test_edges_stay_finite_and_gradients_vanish_where_the_contract_says",
         "test_one_training_step_matches_the_oracle_backward", "test_fit_under_huber_with_mae_matches_the_oracle_fit",
@@ -134,6 +142,10 @@ EQUIVALENCE_TESTS = {
     "test_gpu_optimizers.py": {
         "test_buckets_then_one_advance_equal_the_whole_buffer_step",
         "test_captured_steps_replay_bit_identically_and_advance_t_and_P"},
+    "test_gpu_grad_transforms.py": {
+        "test_buckets_in_any_order_give_the_bits_of_the_whole_buffer", "test_a_captured_step_replays_with_an_advancing_learning_rate",
+        "test_unchanged_paths_keep_their_launches_and_their_bits",
+        "test_fit_with_global_clipnorm_under_rccl_one_rank_equals_single_process"},
     "test_gpu_losses.py": {
         "test_bits_do_not_depend_on_the_call_or_the_block", "test_fit_under_graph_replay_has_the_eager_bits_for_a_new_kind"},
 }
@@ -261,6 +273,61 @@ def build(trace_dir, tests_tsv, out_path):
     print(f"{out_path}: {len(lib_kernels)} kernels, {len(missing)} not launched, {unassigned} dispatches unassigned")
 
 
+def merge(out_path, *part_paths):
+    """One record from the records of parts of the suite that share no test (each part `build`s against the same library):
+    launches and test counts add up, the test lines are re-sorted together ('*' first) and cut to 12 again - every part lists
+    its own first 12 in that order, so the merged first 12 are among them."""
+    import re
+    kernels, order, dispatches, unassigned, other = {}, [], 0, 0, 0
+    for path in part_paths:
+        cur = None
+        for line in open(path):
+            line = line.rstrip("\n")
+            m = re.match(r"# test ranges from: .*; (\d+) dispatches, (\d+) outside", line)
+            if m:
+                dispatches, unassigned = dispatches + int(m.group(1)), unassigned + int(m.group(2))
+            m = re.match(r"# kernels launched by the suite that are not the library's \(torch / RCCL\): (\d+)", line)
+            if m:
+                other = max(other, int(m.group(1)))
+            if line.startswith("KERNEL "):
+                parts = [p.strip() for p in line[len("KERNEL "):].split("  |  ")]
+                if parts[0] not in kernels:
+                    kernels[parts[0]] = dict(dm=parts[1], n=[0, 0, 0, 0], tests={})
+                    order.append(parts[0])
+                cur = kernels[parts[0]]
+                for i in range(4):
+                    cur["n"][i] += int(parts[2 + i])
+            elif cur is not None and line.startswith("    ") and line.rstrip().endswith(")") and "... and" not in line:
+                m = re.match(r"    (.) (.*)  \((\d+)\)$", line)
+                cur["tests"][m.group(2)] = (m.group(1), int(m.group(3)))
+            elif not line.startswith("    "):
+                cur = None
+    lines = ["# kernel coverage of `python -m pytest tests -m gpu` under rocprofv3 --kernel-trace --marker-trace -M",
+             f"# test ranges from: ROCTx ranges (rocprofv3 --marker-trace), {len(part_paths)} parts of the suite merged; {dispatches} dispatches, "
+             f"{unassigned} outside every test range (session set-up)",
+             f"# {len(order)} kernel symbols in libdib_hip.so (gfx950 code object); '*' = the test compares with the float64 / NumPy oracle,",
+             "# '=' = the test demands equality (bits or fp32 summation-order tolerance) with a path that '*' tests check",
+             "# format: KERNEL <mangled>  |  <demangled>  |  launches  |  tests  |  '*' tests  |  '=' tests ; then one line per test (at most 12, '*' first)"]
+    missing = []
+    for k in sorted(order):
+        e = kernels[k]
+        lines.append(f"KERNEL {k}  |  {e['dm']}  |  {e['n'][0]}  |  {e['n'][1]}  |  {e['n'][2]}  |  {e['n'][3]}")
+        if e["n"][1] == 0:
+            missing.append(k)
+        names = sorted(e["tests"], key=lambda t: ("*= ".index(e["tests"][t][0]), t))
+        for t in names[:12]:
+            lines.append(f"    {e['tests'][t][0]} {t}  ({e['tests'][t][1]})")
+        if e["n"][1] > 12:
+            lines.append(f"      ... and {e['n'][1] - 12} more tests")
+    lines.append(f"# kernels launched by the suite that are not the library's (torch / RCCL): {other}")
+    lines.append(f"# library kernels no test launched: {len(missing)}")
+    for k in missing:
+        lines.append(f"MISSING {k}  |  {kernels[k]['dm']}")
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print(f"{out_path}: {len(order)} kernels, {len(missing)} not launched")
+
+
 def read_record(path):
     """{mangled kernel: (launches, number of tests, number of oracle-comparing tests, number of equivalence tests)}"""
     rec = {}
@@ -282,6 +349,8 @@ def check(path):
 if __name__ == "__main__":
     if sys.argv[1] == "build":
         build(*sys.argv[2:5])
+    elif sys.argv[1] == "merge":
+        merge(sys.argv[2], *sys.argv[3:])
     elif sys.argv[1] == "check":
         sys.exit(check(sys.argv[2]))
     elif sys.argv[1] == "list":
