@@ -14,8 +14,11 @@ from .circuit import CircuitIB  # noqa: F401
 from . import random_partition  # noqa: F401
 from .random_partition import RandomPartition  # noqa: F401
 from . import mi_characterization  # noqa: F401
+from . import tabular  # noqa: F401
+from .tabular import TabularPreprocessor  # noqa: F401
 
 __all__ = ["DistributedIBNet", "DistributedIBModule", "InfoBottleneckAnnealingCallback", "SaveCompressionMatricesCallback",
            "InfoPerFeatureCallback", "PositionalEncoding", "Callback", "History", "models", "losses", "optimizers", "schedules", "data", "utils",
            "visualization", "ctw", "chaos_data", "set_transformer", "SetTransformerDIB", "measurement", "MeasurementIB",
-           "circuit", "CircuitIB", "random_partition", "RandomPartition", "mi_characterization"]
+           "circuit", "CircuitIB", "random_partition", "RandomPartition", "mi_characterization",
+           "tabular", "TabularPreprocessor"]

@@ -362,6 +362,16 @@ SIGNATURES_GRAD_TRANSFORM = {
 }
 
 
+# include/dib_tabular.h: the tabular front end's quantile transform
+TABULAR_MIN_QUANTILES, TABULAR_MAX_QUANTILES, TABULAR_MAX_COLS = 2, 10000, 65535
+TABULAR_DISTRIBUTIONS = {"normal": 0, "uniform": 1}
+SIGNATURES_TABULAR = {
+    "dib_quantile_supported": (c_int, [c_int, c_int, c_int]),
+    "dib_quantile_transform": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64,
+                                       c_void_p, c_void_p]),
+}
+
+
 class HostGradTable:
     """The host half of a variable table (include/dib_grad_transform.h): segments, the tile work-list, seg_tile0.  No GPU needed;
     `upload(device)` makes the dib_grad_table the launches take (engine.py, dense.py)."""
@@ -450,7 +460,7 @@ def _attach(lib):
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_ST.items()) + list(SIGNATURES_MEASURE.items()) \
             + list(SIGNATURES_CIRCUIT.items()) + list(SIGNATURES_PARTITION.items()) + list(SIGNATURES_MI_CHANNEL.items()) + list(SIGNATURES_MI_FEATURES.items()) \
             + list(SIGNATURES_COMPRESSION.items()) + list(SIGNATURES_OPTIMIZERS.items()) + list(SIGNATURES_LOSSES.items()) \
-            + list(SIGNATURES_GRAD_TRANSFORM.items()):
+            + list(SIGNATURES_GRAD_TRANSFORM.items()) + list(SIGNATURES_TABULAR.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

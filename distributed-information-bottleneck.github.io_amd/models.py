@@ -289,9 +289,20 @@ class DistributedIBNet:
             self._flat_leaf = eng.params.detach().requires_grad_(True)
         return self._flat_leaf
 
+    @staticmethod
+    def _device_input(eng, x):
+        """fit / evaluate / predict inputs: a float32 tensor already on the engine's device as the row-major matrix the kernels
+        read - itself when it is one, no trip through the host - or None for anything else (the NumPy path)"""
+        if not (isinstance(x, torch.Tensor) and x.device == eng.device and x.dtype == torch.float32):
+            return None
+        x = x.detach()
+        return (x.view(-1, 1) if x.dim() == 1 else x).contiguous()
+
     def predict(self, x, batch_size=None, verbose=0):
         eng = self._ensure_engine()
-        xd = eng.to_device(x)
+        xd = self._device_input(eng, x)
+        if xd is None:
+            xd = eng.to_device(x)
         n = xd.shape[0]
         bs = int(batch_size or 32768)
         outs = []
@@ -486,7 +497,8 @@ class DistributedIBNet:
         eng = self._ensure_engine()
         dist, rank, world = self._dist()
         F = self.number_features
-        x_np = np.asarray(x, dtype=np.float32)
+        xd = self._device_input(eng, x)   # a table already on the device (tabular.TabularPreprocessor) is used where it lies
+        x_np = xd if xd is not None else np.asarray(x, dtype=np.float32)
         if x_np.ndim == 1:
             x_np = x_np[:, None]
         y_np = np.asarray(y, dtype=np.float32)
@@ -495,15 +507,16 @@ class DistributedIBNet:
         assert x_np.shape[-1] == int(np.sum(self.feature_dimensionalities)), "input width != sum(feature dims)"
         n = x_np.shape[0]
         bs = int(batch_size or 32)
-        xd, yd = eng.to_device(x_np), eng.to_device(y_np)
+        xd, yd = xd if xd is not None else eng.to_device(x_np), eng.to_device(y_np)
         if validation_data is not None:
-            xv_np = np.asarray(validation_data[0], dtype=np.float32)
+            xvd = self._device_input(eng, validation_data[0])
+            xv_np = xvd if xvd is not None else np.asarray(validation_data[0], dtype=np.float32)
             yv_np = np.asarray(validation_data[1], dtype=np.float32)
             if xv_np.ndim == 1:
                 xv_np = xv_np[:, None]
             if yv_np.ndim == 1:
                 yv_np = yv_np[:, None]
-            xvd, yvd = eng.to_device(xv_np), eng.to_device(yv_np)
+            xvd, yvd = xvd if xvd is not None else eng.to_device(xv_np), eng.to_device(yv_np)
         track = None
         if track_information is not None:
             track = dict(track_information)
@@ -733,7 +746,9 @@ class DistributedIBNet:
         eng = self._ensure_engine()
         if self.loss is None:
             raise RuntimeError("call compile() before evaluate()")
-        xd = eng.to_device(np.asarray(x, dtype=np.float32))
+        xd = self._device_input(eng, x)
+        if xd is None:
+            xd = eng.to_device(np.asarray(x, dtype=np.float32))
         y_np = np.asarray(y, dtype=np.float32)
         y_np = y_np[:, None] if y_np.ndim == 1 else y_np
         yd = eng.to_device(y_np)

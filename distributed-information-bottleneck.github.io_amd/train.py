@@ -27,7 +27,7 @@ def _bool(v):
 
 def get_args(argv=None):
     p = argparse.ArgumentParser(description="Distributed IB training (MI355X-native)")
-    p.add_argument('--dataset', default='boolean_circuit', choices=['boolean_circuit', 'synthetic_tabular', 'double_pendulum'])
+    p.add_argument('--dataset', default='boolean_circuit', choices=['boolean_circuit', 'synthetic_tabular', 'double_pendulum', 'table'])
     p.add_argument('--data_path', type=str, default='./data/')
     p.add_argument('--artifact_outdir', type=str, default='./training_artifacts/')
     p.add_argument('--ib', type=_bool, default=False, help='vanilla IB: treat all features as one (train.py:111-113)')
@@ -69,6 +69,14 @@ def get_args(argv=None):
     p.add_argument('--boolean_number_input_gates', type=int, default=10)
     p.add_argument('--synthetic_rows', type=int, default=1 << 20)
     p.add_argument('--synthetic_features', type=int, default=64)
+    p.add_argument('--table_path', type=str, default=None,
+                   help="--dataset table: an .npz with x, y and optional columns, or a .csv (data.fetch_table)")
+    p.add_argument('--table_target', type=str, default=None, help='the target column (name or index) when it is part of the table; default the last')
+    p.add_argument('--table_problem', type=str, default='classification', choices=['classification', 'regression'])
+    p.add_argument('--table_categorical', type=str, nargs='*', default=[], help='names or indices of the columns to one-hot')
+    p.add_argument('--table_quantile_noise', type=float, default=1e-3)
+    p.add_argument('--table_n_quantiles', type=int, default=2000)
+    p.add_argument('--table_valid_fraction', type=float, default=0.2)
     p.add_argument('--seed', type=int, default=0, help='noise / init / shuffle seed (the reference is unseeded)')
     p.add_argument('--verbose', type=_bool, default=False)
     return p.parse_args(argv)
@@ -120,7 +128,10 @@ def main(argv=None):
         data_path=args.data_path, boolean_random_circuit=args.boolean_random_circuit,
         boolean_number_input_gates=args.boolean_number_input_gates, synthetic_rows=args.synthetic_rows,
         synthetic_features=args.synthetic_features, pendulum_time_delta=args.pendulum_time_delta,
-        pendulum_number_trajectories=args.pendulum_number_trajectories, seed=args.seed)
+        pendulum_number_trajectories=args.pendulum_number_trajectories, seed=args.seed, table_path=args.table_path,
+        table_target=args.table_target, table_problem=args.table_problem, table_categorical=args.table_categorical,
+        table_quantile_noise=args.table_quantile_noise, table_n_quantiles=args.table_n_quantiles,
+        table_valid_fraction=args.table_valid_fraction)
     if dataset_dict['loss'] == 'infonce' and not args.infonce_loss:
         raise ValueError(f"dataset {args.dataset} trains with --infonce_loss True (reference data.py:131)")
     if rank == 0:

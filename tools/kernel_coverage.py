@@ -100,6 +100,9 @@ ORACLE_TESTS = {
         "test_envelope_matches_the_float64_helper", "test_edges_stay_finite_and_gradients_vanish_where_the_contract_says",
         "test_one_training_step_matches_the_oracle_backward", "test_fit_under_huber_with_mae_matches_the_oracle_fit",
         "test_fit_on_one_hot_labels_with_smoothing_and_accuracy_matches_the_oracle_fit"},
+    "test_gpu_tabular.py": {
+        "test_envelope_matches_the_float64_oracle", "test_crafted_values", "test_fixture_through_the_device_backend",
+        "test_table_end_to_end_against_the_oracle_fit"},
 }
 # tests that demand the bits (or fp32 summation-order tolerance) of a path the tests above check against an oracle
 EQUIVALENCE_TESTS = {
@@ -148,6 +151,9 @@ EQUIVALENCE_TESTS = {
         "test_fit_with_global_clipnorm_under_rccl_one_rank_equals_single_process"},
     "test_gpu_losses.py": {
         "test_bits_do_not_depend_on_the_call_or_the_block", "test_fit_under_graph_replay_has_the_eager_bits_for_a_new_kind"},
+    "test_gpu_tabular.py": {
+        "test_placement_does_not_change_the_bits", "test_graph_replay_has_the_eager_bits",
+        "test_fit_on_a_device_tensor_equals_fit_on_numpy_bit_for_bit"},
 }
 
 
