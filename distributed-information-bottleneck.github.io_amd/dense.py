@@ -16,8 +16,9 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
+from ._flat_optimizer import FlatOptimizer, HoldsFlatOptimizer
 from ._gemm_plan import _Gemm, _d, _ptr, _ptr_array3
-from ._lib import ACTIVATIONS, SYNC_WORDS as _SYNC_WORDS, check
+from ._lib import ACTIVATIONS, check
 
 
 class _MlpDesc(ctypes.Structure):
@@ -38,7 +39,7 @@ def _mlp_desc(w_off: Sequence[int], b_off: Sequence[int], widths: Sequence[int],
     return d
 
 
-class DenseStack:
+class DenseStack(HoldsFlatOptimizer):
     def __init__(self, engine, input_dim: int, units: Sequence[int], output_dim: int, activation: Optional[str] = "relu",
                  use_positional_encoding: bool = True, number_positional_encoding_frequencies: int = 5, seed: int = 0):
         self.eng, self.lib, self.device = engine, engine.lib, engine.device
@@ -57,11 +58,11 @@ class DenseStack:
         for (i, o), w in zip(self.dims, self.w_off):  # Keras glorot-uniform kernels, zero biases
             lim = math.sqrt(6.0 / (i + o))
             flat[w: w + i * o] = rng.uniform(-lim, lim, i * o).astype(np.float32)
-        z = lambda: torch.zeros(off, dtype=torch.float32, device=self.device)
         self.params = torch.from_numpy(flat).to(self.device)
-        self.grads, self.adam_m, self.adam_v = z(), z(), z()
-        self.t_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.lr_dev = torch.full((1,), 1e-3, dtype=torch.float32, device=self.device)
+        self.grads = torch.zeros(off, dtype=torch.float32, device=self.device)
+        self.opt_state = FlatOptimizer(self.lib, engine._stream, off, self.device)
+        self._grad_transform = None   # grad_transform(): made by the first clipped step
+        self._keep = None             # companion_forward's operands, alive until the launch that reads them has been issued
         self._plans: Dict[int, dict] = {}
         self._last: Optional[dict] = None
         # batches <= 2048 rows: the whole layer chain of 16 rows in one workgroup (dib_mlp_small_fwd / _bwd, csrc/dib_small.h)
@@ -69,7 +70,6 @@ class DenseStack:
         if 2 <= len(self.dims) <= 4:
             self._desc = _mlp_desc(self.w_off, self.b_off, [o for _, o in self.dims], self.input_dim, max(self.n_freq, 1), self.act)
         self._unreduced: Optional[dict] = None   # the plan whose slabs a backward(reduce=False) left for the optimizer's launch
-        self._sync: Optional[torch.Tensor] = None   # dib_reduce_adam_step's grid-sync words, allocated by its first call
 
     # views
     def kernel(self, l):
@@ -236,29 +236,20 @@ class DenseStack:
             check(self.lib.dib_reduce_splits(_ptr(pl["slabs"]), self.n_params, pl["nsplit"], self.n_params, _ptr(self.grads), st),
                   "dib_reduce_splits")
 
-    def set_lr(self, lr: float) -> None:
-        self.lr_dev.fill_(float(lr))
-
     def adam_step(self, lr: Optional[float] = None, beta1=0.9, beta2=0.999, eps=1e-7, fused_reduce: bool = False) -> None:
         """lr None: the learning rate last set (set_lr) - a loop with a constant rate sets it once.  fused_reduce=True: one
         launch sums the slabs a backward(reduce=False) left, applies Keras-Adam and bumps the step count
         (dib_reduce_adam_step) instead of reduce + Adam + bump."""
         if lr is not None:
-            self.lr_dev.fill_(float(lr))
+            self.set_lr(lr)
         if fused_reduce:
             pl = self._unreduced
-            if self._sync is None:
-                self._sync = torch.zeros(_SYNC_WORDS, dtype=torch.int32, device=self.device)
-            check(self.lib.dib_reduce_adam_step(_ptr(pl["slabs"]) if pl is not None else None, pl["nsplit"] if pl is not None else 0,
-                                                self.n_params, _ptr(self.params), _ptr(self.grads), _ptr(self.adam_m),
-                                                _ptr(self.adam_v), self.n_params, _ptr(self.lr_dev), _ptr(self.t_dev), beta1,
-                                                beta2, eps, 1.0, _ptr(self._sync), self.eng._stream()), "dib_reduce_adam_step")
+            slabs, nsplit = (pl["slabs"], pl["nsplit"]) if pl is not None else (None, 0)
+            self.opt_state.reduce_adam(slabs, nsplit, self.params, self.grads, self.n_params, beta1, beta2, eps)
             self._unreduced = None
             return
         assert self._unreduced is None, "backward(reduce=False) must be followed by adam_step(fused_reduce=True)"
-        check(self.lib.dib_adam_step(_ptr(self.params), _ptr(self.grads), _ptr(self.adam_m), _ptr(self.adam_v),
-                                     self.n_params, _ptr(self.lr_dev), _ptr(self.t_dev), beta1, beta2, eps, 1.0,
-                                     self.eng._stream()), "dib_adam_step")
+        self.opt_state.adam(self.params, self.grads, self.n_params, beta1, beta2, eps)
 
     def reduce_pending(self) -> None:
         """self.grads <- the fixed-order sum of the slabs a backward(reduce=False) left (nothing when there are none)"""
@@ -271,7 +262,7 @@ class DenseStack:
     def grad_transform(self):
         """gradient clipping on this stack's buffer (include/dib_grad_transform.h): one variable per Dense kernel and bias, in
         layer order; the 4-float alignment gaps after them belong to none"""
-        if getattr(self, "_grad_transform", None) is None:
+        if self._grad_transform is None:
             from . import _lib
             from .grad_transform import GradTransform
             offs, cnts = [], []
@@ -281,51 +272,27 @@ class DenseStack:
             self._grad_transform = GradTransform(self.lib, _lib.HostGradTable(offs, cnts, self.n_params), self.grads, self.eng._stream)
         return self._grad_transform
 
-    def apply_lr(self, descriptor: dict) -> None:
-        """lr_dev <- the schedule at this stack's step count, on the device (dib_lr_schedule_eval)"""
-        from .grad_transform import eval_lr
-        eval_lr(self.lib, descriptor, self.t_dev, self.lr_dev, self.eng._stream())
+    apply_lr = HoldsFlatOptimizer.apply_lr_descriptor   # (the name fit_infonce calls it by)
 
     def optimizer_step(self, opt, lr: Optional[float] = None, transform: bool = True) -> None:
         """One update by any optimizers.Optimizer (the custom loop steps both networks with one Keras optimizer, reference
-        train.py:196,219).  Slabs a backward(reduce=False) left are summed first.  Adam: adam_step, its launches and bits; plain
-        SGD: dib_sgd_step; every other rule: dib_optimizer_step + dib_optimizer_advance (include/dib_optimizers.h) on this
-        stack's own state - adam_m, adam_v, a third buffer allocated when a rule first needs it, its step count and Nadam's P.
-        A change of rule re-initialises that state.  The optimizer's clip arguments transform the final gradient first - a
-        clipped step cannot use the fused sum-and-Adam launch (transform=False: the caller already did, with a norm over both
-        networks)."""
+        train.py:196,219), on this stack's own state; a change of rule re-initialises it, as in HipEngine.  Slabs a
+        backward(reduce=False) left are summed first.  Adam: adam_step; plain SGD: dib_sgd_step; every other rule: dib_optimizer_step
+        + dib_optimizer_advance.  The optimizer's clip arguments transform the final gradient first - a clipped step cannot use
+        the fused sum-and-Adam launch (transform=False: the caller already did, with a norm over both networks)."""
+        st = self.opt_state
+        st.bind(opt)
         if lr is not None:
-            self.lr_dev.fill_(float(lr))
+            st.set_lr(lr)
         if transform and opt.clip() is not None:
             self.reduce_pending()
             self.grad_transform().transform(opt.clip())
         if opt.native and opt.name == "adam":
             self.adam_step(None, opt.beta_1, opt.beta_2, opt.epsilon, fused_reduce=self._unreduced is not None)
             return
-        st = self.eng._stream()
         self.reduce_pending()
         if opt.native:
-            check(self.lib.dib_sgd_step(_ptr(self.params), _ptr(self.grads), self.n_params, _ptr(self.lr_dev), 1.0, st), "dib_sgd_step")
-            return
-        from ._lib import OptimizerHyper
-        hyper = OptimizerHyper(**opt.hyper())
-        slots = opt.slots()
-        if slots > 2 and getattr(self, "opt_s2", None) is None:
-            self.opt_s2 = torch.zeros_like(self.adam_m)
-        bufs = (self.adam_m, self.adam_v, getattr(self, "opt_s2", None))
-        state = [_ptr(bufs[k]) if k < slots else None for k in range(3)]
-        scalar = None
-        if opt.name == "nadam":
-            if getattr(self, "opt_scalar", None) is None:
-                self.opt_scalar = torch.ones(1, dtype=torch.float64, device=self.device)
-            scalar = self.opt_scalar
-        key = (opt.kind, tuple(sorted(opt.hyper().items())))
-        if getattr(self, "_opt_key", None) != key:
-            check(self.lib.dib_optimizer_init(opt.kind, ctypes.byref(hyper), *state, self.n_params, _ptr(scalar), st),
-                  "dib_optimizer_init")
-            self.t_dev.zero_()
-            self._opt_key = key
-        check(self.lib.dib_optimizer_step(opt.kind, ctypes.byref(hyper), _ptr(self.params), _ptr(self.grads), *state, self.n_params,
-                                          _ptr(self.lr_dev), _ptr(self.t_dev), _ptr(scalar), 1.0, st), "dib_optimizer_step")
-        check(self.lib.dib_optimizer_advance(opt.kind, ctypes.byref(hyper), _ptr(self.t_dev), _ptr(scalar), st),
-              "dib_optimizer_advance")
+            st.sgd(self.params, self.grads, self.n_params)
+        else:
+            st.step_range(opt, self.params, self.grads, 0, self.n_params)
+            st.advance(opt)

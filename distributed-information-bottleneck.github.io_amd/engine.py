@@ -16,7 +16,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._flat_optimizer import FlatOptimizer, HoldsFlatOptimizer
 from ._lib import ACTIVATIONS, LOSS_KINDS, check
+from .optimizers import Adam, as_optimizer
 from .utils import mi_sandwich_rows
 
 
@@ -24,7 +26,7 @@ def _ptr(t: Optional[torch.Tensor]):
     return c_void_p(t.data_ptr()) if t is not None else c_void_p(0)
 
 
-class HipEngine:
+class HipEngine(HoldsFlatOptimizer):
     """Owns the flat parameter / gradient / Adam buffers and the activation workspace.
 
     The architecture arguments mirror DistributedIBNet.__init__ (reference models.py:56-66).
@@ -62,11 +64,9 @@ class HipEngine:
         n_alloc = (self.n_params + 3) // 4 * 4
         with torch.cuda.device(self.device):
             z = lambda n, dt=torch.float32: torch.zeros(n, dtype=dt, device=self.device)
-            self.params, self.grads, self.adam_m, self.adam_v = z(n_alloc), z(n_alloc), z(n_alloc), z(n_alloc)
+            self.params, self.grads = z(n_alloc), z(n_alloc)
+            self.opt_state = FlatOptimizer(self.lib, self._stream, n_alloc, self.device)
             self.beta_dev = torch.ones(1, dtype=torch.float32, device=self.device)  # reference models.py:86
-            self.lr_dev = torch.full((1,), 1e-3, dtype=torch.float32, device=self.device)
-            self._lr_host: Optional[float] = 1e-3
-            self.t_dev = z(1, torch.int64)
             # History accumulators: training | validation, one tensor (one device-to-host copy reads both: fit synchronises
             # once per epoch - the validation pass is enqueued behind the training steps without reading anything back)
             self._metrics_stride = (self.F + 3 + 3) // 4 * 4
@@ -86,6 +86,10 @@ class HipEngine:
         self._fused_head: Dict[int, bool] = {}      # loss kind -> dib_output_head_fused_supported
         self._loss_descs: Dict[tuple, "_lib.LossDesc"] = {}   # losses.LossDescriptor -> its checked dib_loss_desc
         self._infonce_ws: Dict[int, torch.Tensor] = {}   # batch -> workspace of dib_infonce_fwd_bwd
+        self._grad_transform = None                 # grad_transform(): made by the first clipped step
+        self._part_segments: Dict[int, tuple] = {}  # gradient bucket -> its (first, number) of variable-table segments
+        self._held_parts: List[int] = []            # global_clipnorm: buckets that have landed, held until the step's last
+        self.step_dev: Optional[torch.Tensor] = None   # enable_step_counter(): the device-resident noise step
         self.blocks = self._query_blocks()
         self.set_flat_params(self.glorot_uniform(init_seed))
 
@@ -93,9 +97,11 @@ class HipEngine:
     def _stream(self):
         return c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    layout = None   # (until __init__ has made it: __del__ also runs on an engine whose __init__ raised)
+
     def __del__(self):
         try:
-            if getattr(self, "layout", None):
+            if self.layout:
                 self.lib.dib_layout_destroy(self.layout)
                 self.layout = None
         except Exception:
@@ -172,89 +178,28 @@ class HipEngine:
     def get_flat_grads(self) -> np.ndarray:
         return self.grads.detach().cpu().numpy().copy()
 
-    def reset_optimizer(self) -> None:
-        """optimizer state as before the first step, by the bound rule (set_optimizer): zeros and t = 0 for Adam / plain SGD;
-        the rule's own start values otherwise (Adagrad's accumulator, Nadam's P = 1: dib_optimizer_init)"""
-        opt = getattr(self, "_opt", None)
-        if opt is None:
-            self.adam_m.zero_()
-            self.adam_v.zero_()
-        else:
-            s = self._opt_state(opt)
-            check(self.lib.dib_optimizer_init(opt.kind, byref(self._opt_hyper(opt)), *(_ptr(b) for b in s), self.adam_m.numel(),
-                                              _ptr(self._opt_scalar(opt)), self._stream()), "dib_optimizer_init")
-        self.t_dev.zero_()
-
-    # ---- the optimizer family beyond Adam / momentum-free SGD (include/dib_optimizers.h) ------------------------------------
-    @staticmethod
-    def _opt_hyper(opt) -> "_lib.OptimizerHyper":
-        return _lib.OptimizerHyper(**opt.hyper())
-
-    @staticmethod
-    def _opt_key(opt):
-        return None if opt is None or opt.native else (opt.kind, tuple(sorted(opt.hyper().items())))
-
-    def _opt_state(self, opt):
-        """the rule's state slots in order: adam_m, adam_v and a third buffer allocated when a rule first needs it"""
-        slots = opt.slots()
-        if slots > 2 and getattr(self, "opt_s2", None) is None:
-            self.opt_s2 = torch.zeros_like(self.adam_m)
-        bufs = (self.adam_m, self.adam_v, getattr(self, "opt_s2", None))
-        return [bufs[k] if k < slots else None for k in range(3)]
-
-    def _opt_scalar(self, opt):
-        """Nadam's running product P of its momentum schedule: one device float64 (None for every other rule)"""
-        if opt.name != "nadam":
-            return None
-        if getattr(self, "opt_scalar", None) is None:
-            self.opt_scalar = torch.ones(1, dtype=torch.float64, device=self.device)
-        return self.opt_scalar
-
-    def set_optimizer(self, opt) -> None:
-        """Bind an optimizers.Optimizer: the state buffers change meaning with the rule, so a CHANGE of rule (kind or
-        hyper-parameters; the learning rate is not one) re-initialises them and the step count.  Binding the rule already bound is
-        free; Adam and momentum-free SGD (`opt.native`) are the engine's initial binding."""
-        key = self._opt_key(opt)
-        if key == self._opt_key(getattr(self, "_opt", None)):
-            return
-        self._opt = None if key is None else opt
-        self.reset_optimizer()
-
-    def optimizer_step_range(self, opt, offset: int, count: int, grad_scale: float = 1.0) -> None:
-        """the rule on the elements [offset, offset + count) of the flat buffers: one launch, reads t and P, writes neither"""
-        sl = lambda b: None if b is None else b[offset:]
-        s = [sl(b) for b in self._opt_state(opt)]
-        check(self.lib.dib_optimizer_step(opt.kind, byref(self._opt_hyper(opt)), _ptr(sl(self.params)), _ptr(sl(self.grads)),
-                                          *(_ptr(b) for b in s), int(count), _ptr(self.lr_dev), _ptr(self.t_dev),
-                                          _ptr(self._opt_scalar(opt)), float(grad_scale), self._stream()), "dib_optimizer_step")
-
-    def optimizer_advance(self, opt) -> None:
-        """ends a step of the rule: t += 1 (and Nadam's P) in a one-thread launch, after every range has been stepped"""
-        check(self.lib.dib_optimizer_advance(opt.kind, byref(self._opt_hyper(opt)), _ptr(self.t_dev), _ptr(self._opt_scalar(opt)),
-                                             self._stream()), "dib_optimizer_advance")
-
     def optimizer_step(self, opt, grad_scale: float = 1.0, transform: bool = True) -> None:
         """One update of the whole flat buffer from self.grads by any optimizers.Optimizer: Adam and momentum-free SGD through
         adam_step / sgd_step (their launches and bits), every other rule through dib_optimizer_step + dib_optimizer_advance.
         The optimizer's clip arguments transform self.grads first (transform=False: the caller already did, e.g. with a norm
         over several buffers)."""
-        self.set_optimizer(opt)
+        st = self.opt_state
+        st.bind(opt)
         if transform and opt.clip() is not None:   # the rule then reads the transformed gradient, grad_scale folded in
             self.transform_gradients(opt, grad_scale)
             grad_scale = 1.0
-        if opt.native:
-            if opt.name == "adam":
-                self.adam_step(opt.beta_1, opt.beta_2, opt.epsilon, grad_scale)
-            else:
-                self.sgd_step(grad_scale)
-            return
-        self.optimizer_step_range(opt, 0, self.n_params, grad_scale)
-        self.optimizer_advance(opt)
+        if not opt.native:
+            st.step_range(opt, self.params, self.grads, 0, self.n_params, grad_scale)
+            st.advance(opt)
+        elif opt.name == "adam":
+            self.adam_step(opt.beta_1, opt.beta_2, opt.epsilon, grad_scale)
+        else:
+            self.sgd_step(grad_scale)
 
     # ---- gradient clipping and learning-rate schedules (include/dib_grad_transform.h) ------------------------------------------
     def grad_transform(self) -> "GradTransform":
         """the variable table of the layout on the device, the tile partials and the ss array: made once per engine"""
-        if getattr(self, "_grad_transform", None) is None:
+        if self._grad_transform is None:
             from .grad_transform import GradTransform
             host = _lib.HostGradTable.from_layout(self.layout, self.grads.numel())
             self._grad_transform = GradTransform(self.lib, host, self.grads, self._stream)
@@ -269,10 +214,9 @@ class HipEngine:
 
     def part_segments(self, part: int):
         """(first, number) of the variable-table segments of gradient bucket `part`: a bucket is a run of whole variables"""
-        cache = self.__dict__.setdefault("_part_segments", {})
-        if part not in cache:
-            cache[part] = self.grad_transform().host.segment_range(*self.part_range(part))
-        return cache[part]
+        if part not in self._part_segments:
+            self._part_segments[part] = self.grad_transform().host.segment_range(*self.part_range(part))
+        return self._part_segments[part]
 
     def apply_lr(self, opt) -> None:
         """the learning rate of the next step: a constant through set_lr (nothing when unchanged); `decay` or a schedule through
@@ -281,30 +225,13 @@ class HipEngine:
         if d is None:
             self.set_lr(opt.learning_rate)
         else:
-            self.apply_lr_descriptor(d)
-
-    def apply_lr_descriptor(self, descriptor: dict) -> None:
-        """lr_dev <- the schedule (fields of dib_lr_schedule) at the device step count; the host cache of set_lr is void after it"""
-        from .grad_transform import eval_lr
-        eval_lr(self.lib, descriptor, self.t_dev, self.lr_dev, self._stream())
-        self.invalidate_lr_cache()
+            self.opt_state.eval_lr(d)
 
     def set_beta(self, v: float) -> None:
         self.beta_dev.fill_(float(v))
 
     def get_beta(self) -> float:
         return float(self.beta_dev.item())
-
-    def set_lr(self, v: float) -> None:
-        """device learning rate; a repeated value costs nothing (fit sets it every step - a 4 us fill kernel per step of the
-        reference's default 140 us B = 128 step otherwise).  `lr_dev` is written ONLY here: the host-side cache below is
-        valid by construction (code that must write the device scalar itself calls invalidate_lr_cache() afterwards)."""
-        if self._lr_host != float(v):
-            self.lr_dev.fill_(float(v))
-            self._lr_host = float(v)
-
-    def invalidate_lr_cache(self) -> None:
-        self._lr_host = None
 
     def to_device(self, a, dtype=torch.float32) -> torch.Tensor:
         if isinstance(a, torch.Tensor):
@@ -365,18 +292,16 @@ class HipEngine:
                   grad_scale: float = 1.0, metrics_acc: Optional[torch.Tensor] = None) -> None:
         """ONE launch for the end of a step (include/dib_hip.h dib_step_tail): any of bucket finalize, the fused head's
         weight-gradient reduce, KL / loss sums, metric accumulation, the optimizer on the bucket and the step-count bump.
-        optimizer: ("adam", beta_1, beta_2, epsilon) or ("sgd",) - adds TAIL_ADAM / TAIL_SGD to `flags`."""
-        b1, b2, eps = 0.9, 0.999, 1e-7
-        if optimizer is not None:
-            if optimizer[0] == "adam":
-                flags |= _lib.TAIL_ADAM
-                b1, b2, eps = (float(v) for v in optimizer[1:4])
-            elif optimizer[0] == "sgd":
-                flags |= _lib.TAIL_SGD
-            else:
-                raise ValueError(f"optimizer {optimizer[0]!r}")
+        optimizer: an Adam or a momentum-free SGD (as_optimizer) - adds TAIL_ADAM / TAIL_SGD; clipping first is the caller's."""
+        opt = None if optimizer is None else as_optimizer(optimizer)
+        if opt is not None and not opt.native:
+            raise ValueError(f"optimizer {opt.name!r}: the tail applies Adam and momentum-free SGD")
+        adam = opt is not None and opt.name == "adam"
+        b1, b2, eps = (opt.beta_1, opt.beta_2, opt.epsilon) if adam else (0.9, 0.999, 1e-7)
+        flags |= 0 if opt is None else _lib.TAIL_ADAM if adam else _lib.TAIL_SGD
+        st = self.opt_state
         check(self.lib.dib_step_tail(self.layout, batch, int(part), int(flags), _ptr(self.params), _ptr(self.grads),
-                                     _ptr(self.adam_m), _ptr(self.adam_v), _ptr(self.lr_dev), _ptr(self.t_dev), b1, b2, eps,
+                                     _ptr(st.m), _ptr(st.v), _ptr(st.lr_dev), _ptr(st.t_dev), b1, b2, eps,
                                      float(grad_scale), _ptr(self.beta_dev), float(inv_global_batch),
                                      _ptr(self.metrics_acc if metrics_acc is None else metrics_acc),
                                      _ptr(self.workspace(batch)), self._stream()), "dib_step_tail")
@@ -384,41 +309,36 @@ class HipEngine:
     def optimizer_step_part(self, batch: int, part: int, optimizer, bump: bool) -> None:
         """the optimizer on ONE gradient bucket (after its all-reduce): the data-parallel fit steps buckets 1 and 2 while
         bucket 3 is still on the wire; the launch with bump=True (the last) advances Adam's step count."""
-        if optimizer[0] == "opt":   # ("opt", Optimizer): a rule of include/dib_optimizers.h, or any rule behind a gradient transform
-            opt = optimizer[1]
-            clip = opt.clip()
-            if clip is not None and clip[1] == _lib.CLIP_GLOBAL_NORM:
-                # the norm is over every bucket: this one's sums of squares now, while later buckets are on the wire; all buckets
-                # are transformed (one launch: together they are the whole table) and stepped after the last has landed
-                gt = self.grad_transform()
-                gt.sumsq(clip, self.part_segments(part))
-                held = self.__dict__.setdefault("_held_parts", [])
-                held.append(part)
-                if not bump:
-                    return
-                assert sum(self.part_segments(p)[1] for p in held) == gt.n_segments, "the buckets of a step cover every variable"
-                gt.apply(clip)
-                parts = list(held)
-                held.clear()
-                for k, p in enumerate(parts):
-                    self._rule_on_part(batch, p, opt, bump=k == len(parts) - 1)
+        opt = as_optimizer(optimizer)
+        clip = opt.clip()
+        if clip is not None and clip[1] == _lib.CLIP_GLOBAL_NORM:
+            # the norm is over every bucket: this one's sums of squares now, while later buckets are on the wire; all buckets
+            # are transformed (one launch: together they are the whole table) and stepped after the last has landed
+            gt, held = self.grad_transform(), self._held_parts
+            gt.sumsq(clip, self.part_segments(part))
+            held.append(part)
+            if not bump:
                 return
-            if clip is not None:   # clipvalue / clipnorm are per variable: the bucket is transformed as soon as it has landed
-                self.grad_transform().transform(clip, self.part_segments(part))
-            self._rule_on_part(batch, part, opt, bump)
+            assert sum(self.part_segments(p)[1] for p in held) == gt.n_segments, "the buckets of a step cover every variable"
+            gt.apply(clip)
+            parts = list(held)
+            held.clear()
+            for k, p in enumerate(parts):
+                self._rule_on_part(batch, p, opt, bump=k == len(parts) - 1)
             return
-        self.step_tail(batch, part, _lib.TAIL_BUMP if (bump and optimizer[0] == "adam") else 0, optimizer=optimizer)
+        if clip is not None:   # clipvalue / clipnorm are per variable: the bucket is transformed as soon as it has landed
+            self.grad_transform().transform(clip, self.part_segments(part))
+        self._rule_on_part(batch, part, opt, bump)
 
     def _rule_on_part(self, batch: int, part: int, opt, bump: bool) -> None:
         """the rule of `opt` on one bucket whose gradient is final in self.grads; bump: the step's last launch of the rule"""
         if opt.native:   # Adam / momentum-free SGD: the tail's update on the bucket (dib_adam_step's expressions), no finalize
-            tup = ("adam", opt.beta_1, opt.beta_2, opt.epsilon) if opt.name == "adam" else ("sgd",)
-            self.step_tail(batch, part, _lib.TAIL_BUMP if (bump and opt.name == "adam") else 0, optimizer=tup)
+            self.step_tail(batch, part, _lib.TAIL_BUMP if (bump and opt.name == "adam") else 0, optimizer=opt)
             return
         off, cnt = self.part_range(part)
-        self.optimizer_step_range(opt, off, cnt)
+        self.opt_state.step_range(opt, self.params, self.grads, off, cnt)
         if bump:
-            self.optimizer_advance(opt)
+            self.opt_state.advance(opt)
 
     def part_range(self, part: int):
         """(offset, count) of gradient bucket `part` in the flat buffers (include/dib_hip.h): 0 = encoder bank,
@@ -440,6 +360,8 @@ class HipEngine:
         Every bucket is finalised by ONE dib_step_tail launch; the LAST of them also carries `finish_flags` (the step's
         deferred KL / loss sums, the metric accumulation - into `metrics_acc`, default the model's History accumulator) and,
         without hooks, the optimizer (`optimizer`, see step_tail)."""
+        opt = None if optimizer is None else as_optimizer(optimizer)
+        bump = _lib.TAIL_BUMP if opt is not None and opt.name == "adam" else 0
         ws = self.workspace(batch)
         st = self._stream()
         FIN = _lib.TAIL_FINALIZE
@@ -456,15 +378,14 @@ class HipEngine:
             else:
                 check(self.lib.dib_backward(self.layout, batch, _ptr(self.params), _ptr(self.grads), _ptr(self.beta_dev),
                                             float(inv_global_batch), bflags, _ptr(ws), st), "dib_backward")
-            self.step_tail(batch, -1, FIN | head | finish_flags | (_lib.TAIL_BUMP if optimizer and optimizer[0] == "adam" else 0),
-                           inv_global_batch, optimizer=optimizer, metrics_acc=metrics_acc)
+            self.step_tail(batch, -1, FIN | head | finish_flags | bump, inv_global_batch, optimizer=opt, metrics_acc=metrics_acc)
             return
         assert companion is None, "a companion pass rides on dib_backward (no bucket hooks)"
         if not integration_done:   # (dib_integration_head_step already ran the integration network's backward)
             fn = self.lib.dib_integration_bwd_hidden if hidden_only else self.lib.dib_integration_bwd
             check(fn(self.layout, batch, _ptr(self.params), _ptr(self.grads), _ptr(ws), st), "dib_integration_bwd")
         if on_integration_grads_ready is not None:
-            assert optimizer is None, "the data-parallel caller steps the optimizer after its all-reduces"
+            assert opt is None, "the data-parallel caller steps the optimizer after its all-reduces"
             self.step_tail(batch, 1, FIN | head)
             off, cnt = self.part_range(1)
             on_integration_grads_ready(self.grads[off: off + cnt])
@@ -485,8 +406,7 @@ class HipEngine:
         if on_integration_grads_ready is not None:
             self.step_tail(batch, 0, FIN | finish_flags, inv_global_batch, metrics_acc=metrics_acc)
         else:
-            self.step_tail(batch, -1, FIN | head | finish_flags | (_lib.TAIL_BUMP if optimizer and optimizer[0] == "adam" else 0),
-                           inv_global_batch, optimizer=optimizer, metrics_acc=metrics_acc)
+            self.step_tail(batch, -1, FIN | head | finish_flags | bump, inv_global_batch, optimizer=opt, metrics_acc=metrics_acc)
 
     def input_grad(self, x: torch.Tensor, row_idx: Optional[torch.Tensor], row0: int, batch: int) -> torch.Tensor:
         """dL/dx [batch, sum_d] of the loss whose parameter gradients the last backward of this batch size wrote (include/dib_hip.h
@@ -524,21 +444,19 @@ class HipEngine:
             fused_head = self._fused_head[kind] = bool(self.lib.dib_output_head_fused_supported(self.layout, kind))
         return fused_head
 
-    fused_optimizer_tail = True   # train_step(optimizer=...) applies the optimizer in the step's last launch
-
     def train_step(self, x, y, row_idx, row0: int, batch: int, seed: int, step: int, loss_kind: str,
                    inv_global_batch: Optional[float] = None, accumulate: bool = True,
                    on_integration_grads_ready=None, on_encoder_front_grads_ready=None, optimizer=None) -> None:
         """fwd + loss + bwd for the local rows; grads (partial sums over local rows / B_global) land in
-        self.grads, ready for the data-parallel all-reduce(sum) and the optimizer step.  optimizer=("adam", b1, b2, eps) /
-        ("sgd",) (single process only): the update is applied by the step's LAST launch, which also reduces the gradient
+        self.grads, ready for the data-parallel all-reduce(sum) and the optimizer step.  optimizer (single process only, anything
+        as_optimizer takes): one that rides_in_tail is applied by the step's LAST launch, which also reduces the gradient
         partials, sums the KL / loss partials and accumulates the History metrics (csrc/dib_tail.h)."""
-        if optimizer is not None and optimizer[0] == "opt":
-            # ("opt", Optimizer), a rule of include/dib_optimizers.h: the step ends with the tail WITHOUT an optimizer flag, then
-            # the rule's launch over the whole buffer, then its advance (two launches more than Adam's fused tail)
+        optimizer = None if optimizer is None else as_optimizer(optimizer)
+        if optimizer is not None and not optimizer.rides_in_tail:
+            # the step ends with the tail WITHOUT an optimizer flag, then optimizer_step: the clip's launches, the rule's, its advance
             self.train_step(x, y, row_idx, row0, batch, seed, step, loss_kind, inv_global_batch, accumulate,
                             on_integration_grads_ready, on_encoder_front_grads_ready, None)
-            self.optimizer_step(optimizer[1])
+            self.optimizer_step(optimizer)
             return
         inv = 1.0 / batch if inv_global_batch is None else inv_global_batch
         kind = LOSS_KINDS[loss_kind] if isinstance(loss_kind, str) else loss_kind   # (a losses.LossDescriptor: dib_loss_fwd_bwd_ex)
@@ -584,7 +502,7 @@ class HipEngine:
     def enable_step_counter(self, value: int = 0) -> None:
         """Key the noise with a DEVICE-resident step counter (dib_layout_set_step_counter) so that a captured step
         can be replayed; from now on the by-value `step` arguments are ignored by the kernels."""
-        if getattr(self, "step_dev", None) is None:
+        if self.step_dev is None:
             self.step_dev = torch.zeros(1, dtype=torch.int32, device=self.device)
             check(self.lib.dib_layout_set_step_counter(self.layout, _ptr(self.step_dev)), "dib_layout_set_step_counter")
         self.set_step_counter(value)
@@ -594,12 +512,15 @@ class HipEngine:
         self.step_dev.fill_(v - (1 << 32) if v >= (1 << 31) else v)  # uint32 bit pattern in an int32 tensor
 
     def capture_step_graph(self, x, y, batch: int, loss_kind: str, inv_global_batch: float, seed: int, train: bool,
-                           optimizer: str = "adam", opt_args=(0.9, 0.999, 1e-7)):
+                           optimizer=None):
         """Capture fwd + loss [+ bwd + optimizer] + metric accumulation + step-counter bump for `batch` rows whose
         dataset indices are read from a fixed staging buffer.  Returns (graph, idx_stage): copy the batch's int32 row
         indices into idx_stage, then graph.replay().  Everything the step reads that changes between replays (beta,
-        lr, Adam t, noise step, row indices) lives in device memory."""
-        assert getattr(self, "step_dev", None) is not None, "call enable_step_counter() first"
+        lr, Adam t, noise step, row indices) lives in device memory.  optimizer: None (Adam()) or one that rides_in_tail."""
+        opt = Adam() if optimizer is None else as_optimizer(optimizer)
+        if not opt.rides_in_tail:
+            raise ValueError(f"optimizer {opt.name!r} does not ride in the step's tail launch: its step is not captured")
+        assert self.step_dev is not None, "call enable_step_counter() first"
         idx_stage = torch.zeros(batch, dtype=torch.int32, device=self.device)
         self.workspace(batch)
         self._ws_pinned.add(batch)  # the graph bakes this workspace's pointer in: never evict it
@@ -611,8 +532,7 @@ class HipEngine:
 
         def body():
             if train:
-                self.train_step(x, y, idx_stage, 0, batch, seed, 0, loss_kind, inv_global_batch,
-                                optimizer=("adam", *opt_args) if optimizer == "adam" else ("sgd",))
+                self.train_step(x, y, idx_stage, 0, batch, seed, 0, loss_kind, inv_global_batch, optimizer=opt)
             else:
                 self.eval_step(x, y, idx_stage, 0, batch, seed, 0, loss_kind, inv_global_batch)
             self.step_dev.add_(1)
@@ -640,13 +560,10 @@ class HipEngine:
             self._ws.pop(unpinned.pop(0))
 
     def adam_step(self, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0) -> None:
-        check(self.lib.dib_adam_step(_ptr(self.params), _ptr(self.grads), _ptr(self.adam_m), _ptr(self.adam_v),
-                                     self.n_params, _ptr(self.lr_dev), _ptr(self.t_dev), beta1, beta2, eps,
-                                     float(grad_scale), self._stream()), "dib_adam_step")
+        self.opt_state.adam(self.params, self.grads, self.n_params, beta1, beta2, eps, grad_scale)
 
     def sgd_step(self, grad_scale=1.0) -> None:
-        check(self.lib.dib_sgd_step(_ptr(self.params), _ptr(self.grads), self.n_params, _ptr(self.lr_dev),
-                                    float(grad_scale), self._stream()), "dib_sgd_step")
+        self.opt_state.sgd(self.params, self.grads, self.n_params, grad_scale)
 
     def read_metrics(self, reset: bool = True) -> np.ndarray:
         m = self.metrics_acc.detach().cpu().numpy().astype(np.float64)

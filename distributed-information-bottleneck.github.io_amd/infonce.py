@@ -179,12 +179,10 @@ def fit_infonce(model, x_train, y_train, x_valid, y_valid, *, batch_size: int, n
     superset.  `output_encoder`: a pre-built Y encoder (default: a fresh DenseStack seeded with seed + 1).  `shuffle_buffer`: the
     reference's 10 000 (train.py:227); tools/stream_effect.py passes the dataset length to measure what the buffer does.
     `optimizer`: an optimizers.Optimizer or a Keras name (reference train.py:128-129 builds ONE optimizer for both branches); both
-    networks step with it and with the same step count, at `learning_rate`.  None: Keras-Adam defaults, today's launches."""
+    networks step with it and with the same step count, at `learning_rate`.  None: optimizers.Adam()."""
     eng = model._ensure_engine()
     from . import optimizers as _optimizers
-    opt = None if optimizer is None else _optimizers.get(optimizer)
-    if opt is not None:
-        eng.set_optimizer(opt)
+    opt = _optimizers.Adam() if optimizer is None else _optimizers.get(optimizer)
     assert model.output_dimensionality == shared_dimensionality, "model output must be the shared embedding space"
     F = model.number_features
     xd, yd = eng.to_device(np.asarray(x_train, dtype=np.float32)), eng.to_device(np.asarray(y_train, dtype=np.float32))
@@ -193,6 +191,8 @@ def fit_infonce(model, x_train, y_train, x_valid, y_valid, *, batch_size: int, n
         eng, yd.shape[1], list(y_encoder_architecture), shared_dimensionality, activation_fn,
         use_positional_encoding, number_positional_encoding_frequencies, seed=seed + 1)
     model.output_encoder = yenc
+    eng.set_optimizer(opt)    # a change of rule since the last loop or fit re-initialises the state ...
+    yenc.set_optimizer(opt)   # ... of both networks (the encoder may be a re-used one)
     n, nv = xd.shape[0], xvd.shape[0]
     # data parallel (one process per GPU): every rank draws the same global batch (same seed) and takes its row shard;
     # embeddings are all-gathered for the in-batch negatives, parameter gradients all-reduced (sum)
@@ -234,10 +234,10 @@ def fit_infonce(model, x_train, y_train, x_valid, y_valid, *, batch_size: int, n
     yenc.set_lr(learning_rate)
     # ... unless the optimizer carries `decay` or a schedule: then each network's rate is evaluated on the device from its own step
     # count ahead of every training step (the two counts advance together); `decay` starts from this loop's learning_rate
-    lr_desc = None if opt is None else opt.lr_schedule()
+    lr_desc = opt.lr_schedule()
     if lr_desc is not None and not isinstance(opt.learning_rate, _optimizers._schedules.LearningRateSchedule):
         lr_desc = dict(lr_desc, initial=float(learning_rate))
-    clip = None if opt is None else opt.clip()
+    clip = opt.clip()
     if clip is not None and clip[1] == _optimizers.CLIP_GLOBAL_NORM:
         # one gradient list over both networks (train.py:196-219): their sums of squares share one array, the norm is over it
         ge, gy = eng.grad_transform(), yenc.grad_transform()
@@ -245,31 +245,26 @@ def fit_infonce(model, x_train, y_train, x_valid, y_valid, *, batch_size: int, n
         ge.bind_ss(ss_all, 0)
         gy.bind_ss(ss_all, ge.n_segments)
 
+    # Adam rides in the X model's tail launch and in the Y encoder's sum-and-Adam launch, which knows no other rule
+    in_tail = opt.rides_in_tail and opt.name == "adam"
+
     def step_both():
         """both networks' update by `opt` from their final gradients, the clip arguments applied first"""
-        if clip is None:
-            eng.optimizer_step(opt)
-            yenc.optimizer_step(opt)
-            return
-        yenc.reduce_pending()   # clipping reads the Y encoder's final gradient: the fixed-order sum of its partials
-        ge, gy = eng.grad_transform(), yenc.grad_transform()
-        if clip[1] == _optimizers.CLIP_GLOBAL_NORM:
-            ge.sumsq(clip)
-            gy.sumsq(clip)
-            ge.apply(clip)
-            gy.apply(clip)
-        else:
-            ge.transform(clip)
-            gy.transform(clip)
-        eng.optimizer_step(opt, transform=False)
+        if clip is not None:
+            yenc.reduce_pending()   # clipping reads the Y encoder's final gradient: the fixed-order sum of its partials
+            ge, gy = eng.grad_transform(), yenc.grad_transform()
+            if clip[1] == _optimizers.CLIP_GLOBAL_NORM:
+                ge.sumsq(clip)
+                gy.sumsq(clip)
+                ge.apply(clip)
+                gy.apply(clip)
+            else:
+                ge.transform(clip)
+                gy.transform(clip)
+        eng.optimizer_step(opt, transform=False)   # (Adam and plain SGD: adam_step's / sgd_step's launches)
         yenc.optimizer_step(opt, transform=False)
 
     from . import _lib
-    adam = ("adam", 0.9, 0.999, 1e-7)                             # tf.keras.optimizers.Adam defaults (train.py:128-129)
-    if opt is not None and opt.native and opt.name == "adam":
-        adam = ("adam", opt.beta_1, opt.beta_2, opt.epsilon)
-    # Adam rides in the step's tail launch - unless its gradient is clipped first
-    tail_opt = adam if opt is None or (opt.native and opt.name == "adam" and clip is None) else None
     slots = _LossSlots(eng.device, eng.metrics_acc.dtype)
     # single process: the per-feature KL of every step is accumulated on the device by the step's LAST launch (metrics_acc[f] +=
     # KL_f sum / B, dib_step_tail) - training and validation into accumulators of THIS loop, read once per epoch boundary.
@@ -297,11 +292,11 @@ def fit_infonce(model, x_train, y_train, x_valid, y_valid, *, batch_size: int, n
                     yenc.apply_lr(lr_desc)
                 compb = yenc.companion_backward(gy) if comp is not None else None
                 eng.backward_from_pred_grad(gx, idx, 0, B, model.noise_seed, step, inv_global_batch=1.0 / batch_size,
-                                            finish_flags=_lib.TAIL_KL | _lib.TAIL_METRICS, optimizer=tail_opt, metrics_acc=kl_acc["kl"],
-                                            **({} if compb is None else dict(companion=compb)))
+                                            finish_flags=_lib.TAIL_KL | _lib.TAIL_METRICS, optimizer=opt if in_tail else None,
+                                            metrics_acc=kl_acc["kl"], **({} if compb is None else dict(companion=compb)))
                 yenc.backward(gy, reduce=False, **({} if compb is None else dict(dgrad_done=True)))
-                if tail_opt is not None:
-                    yenc.adam_step(None, *adam[1:], fused_reduce=True)   # one Keras Adam over all variables (train.py:196,219)
+                if in_tail:                                        # one Keras Adam over all variables (train.py:196,219)
+                    yenc.adam_step(None, opt.beta_1, opt.beta_2, opt.epsilon, fused_reduce=True)
                 else:                                              # any other rule: the same optimizer, the same t, both networks
                     step_both()
             else:
@@ -323,11 +318,7 @@ def fit_infonce(model, x_train, y_train, x_valid, y_valid, *, batch_size: int, n
             if lr_desc is not None:
                 eng.apply_lr_descriptor(lr_desc)
                 yenc.apply_lr(lr_desc)
-            if opt is None:
-                eng.adam_step()                                    # one Keras Adam over all variables (train.py:196,219)
-                yenc.adam_step()
-            else:
-                step_both()
+            step_both()                                            # one Keras optimizer over all variables (train.py:196,219)
         return loss, kl
 
     def epoch_mean(name, values):

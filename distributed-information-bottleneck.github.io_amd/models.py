@@ -429,18 +429,8 @@ class DistributedIBNet:
             return dist, dist.get_rank(), dist.get_world_size()
         return None, 0, 1
 
-    def _optimizer_tuple(self):
-        """what HipEngine.train_step / optimizer_step_part take: Adam and momentum-free SGD ride in the step tail; every other
-        rule (optimizers.Optimizer.native is False) and every rule behind a gradient transform (clipvalue, clipnorm,
-        global_clipnorm: the transform launches run between the tail and the update) is ("opt", optimizer)"""
-        opt = self.optimizer
-        if not opt.native or opt.clip() is not None:
-            return ("opt", opt)
-        return ("adam", opt.beta_1, opt.beta_2, opt.epsilon) if opt.name == "adam" else ("sgd",)
-
     def _set_lr(self, eng):
-        """the learning rate of the next step on the device: a constant is set from the host (free when unchanged); `decay` or a
-        schedule is evaluated on the device from the step count (HipEngine.apply_lr, include/dib_grad_transform.h)"""
+        """the next step's learning rate on the device: a constant (free when unchanged), `decay` or a schedule (HipEngine.apply_lr)"""
         opt = self.optimizer
         if opt.lr_schedule() is None:
             eng.set_lr(opt.learning_rate)
@@ -448,14 +438,8 @@ class DistributedIBNet:
             eng.apply_lr(opt)
 
     def _optimizer_step(self, eng):
-        opt = self.optimizer
         self._set_lr(eng)
-        if not opt.native or opt.clip() is not None:
-            eng.optimizer_step(opt)
-        elif opt.name == "adam":
-            eng.adam_step(opt.beta_1, opt.beta_2, opt.epsilon)
-        else:
-            eng.sgd_step()
+        eng.optimizer_step(self.optimizer)
 
     def _epoch_logs(self, acc: np.ndarray, nsteps: int, prefix: str) -> Dict[str, float]:
         """History accounting (reference models.py:115,121; train.py:169-172):
@@ -572,16 +556,12 @@ class DistributedIBNet:
         # (the rules of include/dib_optimizers.h and every step behind a gradient transform always run eagerly: their step is not
         # part of capture_step_graph; a schedule alone keeps the captured step - its one-thread launch goes ahead of each replay)
         use_graphs = (dist is None and hasattr(eng, "capture_step_graph") and bs <= 8192 and n_full * epochs >= 64
-                      and self.optimizer.native and self.optimizer.clip() is None
-                      and os.environ.get("DIB_ENABLE_GRAPHS", "0") == "1")
+                      and self.optimizer.rides_in_tail and os.environ.get("DIB_ENABLE_GRAPHS", "0") == "1")
         graphs = {}
         if use_graphs:
             eng.enable_step_counter(self._step)
             self._set_lr(eng)
-            opt_args = ((self.optimizer.beta_1, self.optimizer.beta_2, self.optimizer.epsilon)
-                        if self.optimizer.name == "adam" else ())
-            graphs["train"] = eng.capture_step_graph(xd, yd, bs, kind, 1.0 / bs, self.noise_seed, True,
-                                                     self.optimizer.name, opt_args)
+            graphs["train"] = eng.capture_step_graph(xd, yd, bs, kind, 1.0 / bs, self.noise_seed, True, self.optimizer)
             eng.set_step_counter(self._step)
         elif getattr(eng, "step_dev", None) is not None:
             eng.set_step_counter(self._step)
@@ -620,7 +600,7 @@ class DistributedIBNet:
                     #   3 last encoder layer    - the only exposed one                                (dp_buckets == 3)
                     #   0 = 2 + 3 as one bucket after the backward                                    (dp_buckets == 2)
                     pending = []
-                    nb = self.dp_buckets if (dist is not None and hasattr(eng, "part_range")) else 1
+                    nb = self.dp_buckets if dist is not None else 1
                     if nb > 1 and gb // world <= self.dp_small_batch_rows:
                         # small per-rank batches (<= 1024 rows: a handful of kernels per step, one grouped launch for every weight
                         # gradient): the backward is a handful of launches with nothing to hide an all-reduce under - one
@@ -628,12 +608,13 @@ class DistributedIBNet:
                         # GLOBAL batch: identical on every rank.
                         nb = 1
                     issue = lambda g: pending.append(dist.all_reduce(g, async_op=True))
-                    if dist is None and getattr(eng, "fused_optimizer_tail", False):
+                    if dist is None:
                         # one process: the step's LAST launch reduces the gradient partials, sums the KL / loss partials,
-                        # accumulates the History metrics and applies the optimizer (csrc/dib_tail.h)
+                        # accumulates the History metrics and applies the optimizer (csrc/dib_tail.h) - or the engine steps an
+                        # optimizer that does not ride there right behind it
                         self._set_lr(eng)
                         eng.train_step(xd, yd, order_dev[s0: s0 + gb], 0, gb, self.noise_seed, self._step, kind,
-                                       inv_global_batch=1.0 / gb, optimizer=self._optimizer_tuple())
+                                       inv_global_batch=1.0 / gb, optimizer=self.optimizer)
                         self._step += 1
                         nsteps += 1
                         if getattr(eng, "step_dev", None) is not None:
@@ -651,22 +632,16 @@ class DistributedIBNet:
                     if nb >= 2:
                         off, cnt = eng.part_range(3 if nb == 3 else 0)
                         issue(eng.grads[off: off + cnt])
-                        if hasattr(eng, "optimizer_step_part"):
-                            # each bucket is stepped as soon as ITS all-reduce has landed: buckets 1 (and 2) are updated on
-                            # the compute stream while the last bucket is still on the wire; every launch reads the same
-                            # Adam step count, the last one advances it
-                            self._set_lr(eng)
-                            parts = (1, 2, 3) if nb == 3 else (1, 0)
-                            for k, (w, part) in enumerate(zip(pending, parts)):
-                                w.wait()
-                                eng.optimizer_step_part(max(hi - lo, 1), part, self._optimizer_tuple(), bump=k == len(parts) - 1)
-                        else:
-                            for w in pending:
-                                w.wait()
-                            self._optimizer_step(eng)
+                        # each bucket is stepped as soon as ITS all-reduce has landed: buckets 1 (and 2) are updated on
+                        # the compute stream while the last bucket is still on the wire; every launch reads the same
+                        # Adam step count, the last one advances it
+                        self._set_lr(eng)
+                        parts = (1, 2, 3) if nb == 3 else (1, 0)
+                        for k, (w, part) in enumerate(zip(pending, parts)):
+                            w.wait()
+                            eng.optimizer_step_part(max(hi - lo, 1), part, self.optimizer, bump=k == len(parts) - 1)
                     else:
-                        if dist is not None:
-                            dist.all_reduce(eng.grads)
+                        dist.all_reduce(eng.grads)
                         self._optimizer_step(eng)
                     self._step += 1
                     nsteps += 1

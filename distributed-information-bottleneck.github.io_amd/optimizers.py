@@ -116,15 +116,21 @@ class Optimizer:
     def clip(self):
         """None, or (clipvalue or 0.0, DIB_CLIP_* mode, norm threshold): the transform of include/dib_grad_transform.h that runs on
         the aggregated gradient before the rule.  An optimizer with one never rides in the step tail."""
-        if self.clipnorm is None and self.global_clipnorm is None and self.clipvalue is None:
+        norm, value, global_norm = self._clip["clipnorm"], self._clip["clipvalue"], self._clip["global_clipnorm"]
+        if norm is None and global_norm is None and value is None:
             return None
-        mode = CLIP_NORM if self.clipnorm is not None else CLIP_GLOBAL_NORM if self.global_clipnorm is not None else CLIP_NONE
-        return (self.clipvalue or 0.0, mode, self.clipnorm or self.global_clipnorm or 0.0)
+        mode = CLIP_NORM if norm is not None else CLIP_GLOBAL_NORM if global_norm is not None else CLIP_NONE
+        return (value or 0.0, mode, norm or global_norm or 0.0)
 
     @property
     def native(self) -> bool:
         """True: dib_adam_step / dib_sgd_step and the step tail's DIB_TAIL_ADAM / DIB_TAIL_SGD apply the rule"""
         return self.kind == 0
+
+    @property
+    def rides_in_tail(self) -> bool:
+        """the step's LAST launch applies this optimizer (DIB_TAIL_ADAM / DIB_TAIL_SGD); else launches of its own follow the tail"""
+        return self.native and self.clip() is None
 
     def hyper(self) -> dict:
         """fields of include/dib_optimizers.h dib_optimizer_hyper"""
@@ -262,6 +268,21 @@ class Nadam(Adamax):
 
 _BY_NAME = {"adam": Adam, "sgd": SGD, "rmsprop": RMSprop, "adagrad": Adagrad, "adadelta": Adadelta, "adamax": Adamax,
             "nadam": Nadam}
+_LEGACY = {}   # ("adam", beta_1, beta_2, epsilon) / ("sgd",) -> its Optimizer: as_optimizer on a hot path is one dict lookup
+
+
+def as_optimizer(x) -> Optimizer:
+    """The Optimizer the engine's step entries work on: `x` itself, or the Adam / momentum-free SGD of the legacy tuples
+    ("adam", beta_1, beta_2, epsilon) / ("sgd",) - one object per tuple, made on first sight.  Anything else: ValueError."""
+    try:
+        return x if isinstance(x, Optimizer) else _LEGACY[x]
+    except (KeyError, TypeError):   # (not seen yet, or nothing that can be a key)
+        pass
+    if isinstance(x, tuple) and len(x) == 4 and x[0] == "adam" and all(isinstance(v, (int, float)) for v in x[1:]):
+        return _LEGACY.setdefault(x, Adam(beta_1=x[1], beta_2=x[2], epsilon=x[3]))
+    if x == ("sgd",):
+        return _LEGACY.setdefault(x, SGD())
+    raise ValueError(f"not an optimizer: {x!r} (an optimizers.Optimizer, ('adam', beta_1, beta_2, epsilon) or ('sgd',))")
 
 
 def build(cls, *args, **kwargs) -> Optimizer:

@@ -5,6 +5,7 @@ import numpy as np
 import torch
 
 import dib_oracle as orc
+from dib_amd.optimizers import as_optimizer
 from _helpers import flat_to_params, params_to_flat
 
 
@@ -81,7 +82,14 @@ class OracleEngine:
         tail = min(b["offset"] for b in self.blocks if b["net"] == 0 and b["layer"] == last)
         return {0: (0, split), 1: (split, self.n_params - split), 2: (0, tail), 3: (tail, split - tail)}[part]
 
-    fused_optimizer_tail = True   # same engine contract as HipEngine: train_step(optimizer=...) applies the update itself
+    def optimizer_step(self, optimizer):
+        """the whole-buffer update: Adam or momentum-free SGD, the rules this engine knows (an Optimizer or a legacy tuple)"""
+        opt = as_optimizer(optimizer)
+        assert opt.rides_in_tail, opt.name
+        if opt.name == "adam":
+            self.adam_step(opt.beta_1, opt.beta_2, opt.epsilon)
+        else:
+            self.sgd_step()
 
     def train_step(self, x, y, row_idx, row0, batch, seed, step, loss_kind, inv_global_batch=None, accumulate=True,
                    on_integration_grads_ready=None, on_encoder_front_grads_ready=None, optimizer=None):
@@ -103,10 +111,7 @@ class OracleEngine:
             self._account(c, task, yb, loss_kind, batch, inv)
         if optimizer is not None:
             assert on_integration_grads_ready is None and on_encoder_front_grads_ready is None
-            if optimizer[0] == "adam":
-                self.adam_step(*optimizer[1:4])
-            else:
-                self.sgd_step()
+            self.optimizer_step(optimizer)
 
     def optimizer_step_part(self, batch, part, optimizer, bump):
         """the optimizer on ONE gradient bucket; every call of a step sees the same Adam step count, `bump` advances it"""
@@ -116,17 +121,14 @@ class OracleEngine:
         flat = lambda q: params_to_flat(self.blocks, q, self.n_params, np.float64)
         before = [flat(self.p), flat(self.state.m), flat(self.state.v)]
         t0 = self.state.t
-        if optimizer[0] == "adam":
-            self.adam_step(*optimizer[1:4])
-        else:
-            self.sgd_step()
+        self.optimizer_step(optimizer)
         after = [flat(self.p), flat(self.state.m), flat(self.state.v)]
         for a, b in zip(after, before):
             a[keep] = b[keep]
         self.p = flat_to_params(self.blocks, after[0], self.spec)
         self.state.m = flat_to_params(self.blocks, after[1], self.spec)
         self.state.v = flat_to_params(self.blocks, after[2], self.spec)
-        self.state.t = t0 + 1 if (bump and optimizer[0] == "adam") else t0
+        self.state.t = t0 + 1 if (bump and as_optimizer(optimizer).name == "adam") else t0
 
     def eval_step(self, x, y, row_idx, row0, batch, seed, step, loss_kind, inv_global_batch=None, metrics_acc=None):
         inv = 1.0 / batch if inv_global_batch is None else inv_global_batch

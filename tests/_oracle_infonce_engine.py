@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 import dib_oracle as orc
+from dib_amd.optimizers import as_optimizer
 from dib_torch_cpu import TorchCpuDIB, scaled_similarity_torch
 from infonce_loop_oracle import YEncoder
 
@@ -43,6 +44,13 @@ class _FlatAdam:
             for p in self.vars:
                 p.sub_(upd[off: off + p.numel()].view_as(p))
                 off += p.numel()
+
+    def set_optimizer(self, opt):
+        assert opt.rides_in_tail and opt.name == "adam", "the checker knows Adam alone"
+
+    def optimizer_step(self, opt, transform=True):
+        self.set_optimizer(opt)
+        self.adam_step(None, opt.beta_1, opt.beta_2, opt.epsilon)
 
     def flat_params(self):
         return torch.cat([p.detach().reshape(-1) for p in self.vars]).numpy().copy()
@@ -118,8 +126,7 @@ class CheckerXEngine(_FlatAdam):
             acc = self.metrics_acc if metrics_acc is None else metrics_acc
             acc[: self.F] += self._kl.detach() * batch * inv
         if optimizer is not None:
-            assert optimizer[0] == "adam"
-            self.adam_step(None, *optimizer[1:4])
+            self.optimizer_step(as_optimizer(optimizer))
 
 
 class CheckerYEncoder(_FlatAdam):

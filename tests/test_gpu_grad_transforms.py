@@ -187,7 +187,7 @@ def test_buckets_in_any_order_give_the_bits_of_the_whole_buffer():
                 e.grads.copy_(flat * (step + 1))
             a.optimizer_step(opt)
             for k, part in enumerate((1, 2, 3)):
-                b.optimizer_step_part(16, part, ("opt", opt), bump=k == 2)
+                b.optimizer_step_part(16, part, opt, bump=k == 2)
             torch.cuda.synchronize()
             for name in ("params", "grads", "adam_m", "adam_v", "t_dev"):
                 assert torch.equal(getattr(a, name), getattr(b, name)), (opt.name, step, name)
@@ -546,14 +546,14 @@ def test_unchanged_paths_keep_their_launches_and_their_bits():
     launches(None)
     base = launches(None)
     assert launches(("adam", 0.9, 0.999, 1e-7)) == base and launches(("sgd",)) == base
-    assert launches(("opt", O.build(O.Adam, clipnorm=1.0))) == base + 3 + 2            # tile sums, segment sums, apply; dib_adam_step's two
-    assert launches(("opt", O.build(O.Adam, global_clipnorm=1.0))) == base + 3 + 2
-    assert launches(("opt", O.build(O.SGD, clipvalue=1.0))) == base + 1 + 1            # apply; dib_sgd_step
+    assert launches(O.build(O.Adam, clipnorm=1.0)) == base + 3 + 2            # tile sums, segment sums, apply; dib_adam_step's two
+    assert launches(O.build(O.Adam, global_clipnorm=1.0)) == base + 3 + 2
+    assert launches(O.build(O.SGD, clipvalue=1.0)) == base + 1 + 1            # apply; dib_sgd_step
     model = dib_amd.DistributedIBNet(**spec_kwargs(spec), noise_seed=4, shuffle_seed=6, init_seed=2)
     for opt, tup in ((O.Adam(), "adam"), (O.Adam(dib_amd.schedules.CosineDecay(1e-3, 10)), "adam"), (O.build(O.SGD, decay=0.1), "sgd"),
-                     (O.build(O.Adam, clipvalue=1.0), "opt")):
+                     (O.build(O.Adam, clipvalue=1.0), None)):   # (None: does not ride in the tail)
         model.compile(optimizer=opt, loss=dib_amd.losses.BinaryCrossentropy(from_logits=True))
-        assert model._optimizer_tuple()[0] == tup
+        assert model.optimizer.rides_in_tail == (tup is not None) and tup in (None, model.optimizer.name)
     xs, ys = orc.boolean_circuit_truth_table([0, 1, 2, 3, [0, 2, 0], [2, 4, 3], [0, 5, 1]], 4)
     xs, ys = np.tile(xs, (3, 1)).astype(np.float32), np.tile(ys, 3).astype(np.float32)
     out = []

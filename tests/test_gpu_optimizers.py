@@ -175,7 +175,7 @@ def test_buckets_then_one_advance_equal_the_whole_buffer_step(case):
             eng.grads.copy_(g)
         a.optimizer_step(opt)
         for k, part in enumerate((1, 2, 3)):
-            b.optimizer_step_part(16, part, ("opt", opt), bump=k == 2)
+            b.optimizer_step_part(16, part, opt, bump=k == 2)
         torch.cuda.synchronize()
         if step in (0, 2):
             for name in ("params", "adam_m", "adam_v", "opt_s2", "opt_scalar", "t_dev"):
@@ -373,10 +373,127 @@ def test_adam_and_plain_sgd_keep_their_launches():
     assert launches(("adam", 0.9, 0.999, 1e-7)) == base and launches(("sgd",)) == base
     rms = O.RMSprop()
     eng.set_optimizer(rms)                                   # (binding a rule fills its state: one launch, not a step's)
-    assert launches(("opt", rms)) == base + 2                # the rule's launch and its advance
+    assert launches(rms) == base + 2                # the rule's launch and its advance
     n0 = eng.lib.dib_launch_count()
     eng.optimizer_step(O.Adam())
     assert eng.lib.dib_launch_count() - n0 == 2
     eng.optimizer_step(O.SGD())
     assert eng.lib.dib_launch_count() - n0 == 3
     torch.cuda.synchronize()
+
+
+# ---- one state object, one encoding --------------------------------------------------------------------------------------
+def _engine(seed=0):
+    from dib_amd.engine import HipEngine
+    return HipEngine(**spec_kwargs(SPECS["boolean4_32x32"]), init_seed=seed)
+
+
+def _same_state(a, b, names=("params", "adam_m", "adam_v", "opt_s2", "opt_scalar", "t_dev")):
+    torch.cuda.synchronize()
+    for name in names:
+        ta, tb = getattr(a, name), getattr(b, name)
+        assert (ta is None) == (tb is None) and (ta is None or torch.equal(ta, tb)), name
+
+
+@pytest.mark.parametrize("legacy", [("adam", 0.9, 0.999, 1e-7), ("sgd",)], ids=["adam", "sgd"])
+def test_legacy_tuple_and_object_are_one_optimizer(legacy):
+    """train_step and optimizer_step_part take the legacy tuple or the Optimizer it stands for: the same launches, the same bits"""
+    from dib_amd import optimizers as O
+    obj = O.Adam() if legacy[0] == "adam" else O.SGD()
+    a, b = _engine(3), _engine(3)
+    rng = np.random.default_rng(0)
+    B = 16
+    x = rng.standard_normal((B, 4)).astype(np.float32)
+    y = (rng.random((B, 1)) > 0.5).astype(np.float32)
+    counts = []
+    for eng, optimizer in ((a, legacy), (b, obj)):
+        xd, yd = eng.to_device(x), eng.to_device(y)
+        eng.train_step(xd, yd, None, 0, B, 1, 0, "bce_logits", optimizer=None)   # workspace set-up
+        n0 = eng.lib.dib_launch_count()
+        for step in range(2):
+            eng.train_step(xd, yd, None, 0, B, 1, step, "bce_logits", optimizer=optimizer)
+        counts.append(eng.lib.dib_launch_count() - n0)
+    assert counts[0] == counts[1]
+    _same_state(a, b)
+    assert int(a.t_dev.item()) == (2 if legacy[0] == "adam" else 0)
+    assert not torch.equal(a.params, torch.from_numpy(a.glorot_uniform(3)).to(a.params.device))
+    g = torch.from_numpy((rng.standard_normal(a.params.numel()) * 1e-2).astype(np.float32))
+    counts = []
+    for eng, optimizer in ((a, legacy), (b, obj)):
+        eng.grads.copy_(g)
+        n0 = eng.lib.dib_launch_count()
+        for k, part in enumerate((1, 2, 3)):
+            eng.optimizer_step_part(B, part, optimizer, bump=k == 2)
+        counts.append(eng.lib.dib_launch_count() - n0)
+    assert counts[0] == counts[1] > 0
+    _same_state(a, b)
+    assert int(a.t_dev.item()) == (3 if legacy[0] == "adam" else 0)
+
+
+def test_dense_stack_reinitialises_its_state_on_a_change_of_rule():
+    """DenseStack binds rules as HipEngine does: RMSprop steps, then Adam, is Adam from scratch (zero moments, t = 0), and the
+    same RMSprop again is RMSprop from scratch"""
+    from dib_amd import optimizers as O
+    from dib_amd.dense import DenseStack
+    eng = _engine()
+    make = lambda: DenseStack(eng, 3, [32], 8, "relu", True, 5, seed=1)
+    a, b, c = make(), make(), make()
+    p0 = a.params.clone()
+    rng = np.random.default_rng(5)
+    g = [torch.from_numpy((rng.standard_normal(a.n_params) * 1e-2).astype(np.float32)).to(a.device) for _ in range(2)]
+    rms, lr = O.RMSprop(momentum=0.5, centered=True), 1e-2
+
+    def steps(stack, opt):
+        for k in range(2):
+            stack.grads.copy_(g[k])
+            stack.optimizer_step(opt, lr=lr)
+
+    steps(a, rms)
+    assert int(a.t_dev.item()) == 2 and a.opt_s2 is not None and float(a.adam_v.abs().max().item()) > 0.0
+    a.params.copy_(p0)
+    steps(a, O.Adam())
+    steps(b, O.Adam())
+    _same_state(a, b, ("params", "adam_m", "adam_v", "t_dev"))
+    assert int(a.t_dev.item()) == int(b.t_dev.item()) == 2
+    assert not torch.equal(a.params, p0)
+    a.params.copy_(p0)
+    steps(a, rms)                     # the SAME object as before: the Adam steps in between were a change of rule
+    steps(c, rms)
+    _same_state(a, c)
+    assert int(a.t_dev.item()) == 2
+
+
+def test_dense_stack_and_the_c_entries_agree_on_nadam():
+    """3 Nadam steps of a DenseStack against the same steps through the C entries on buffers of the test's own (Flat)"""
+    from dib_amd import optimizers as O
+    from dib_amd.dense import DenseStack
+    stack = DenseStack(_engine(), 3, [32], 8, "relu", True, 5, seed=1)
+    n, opt, lr = stack.n_params, O.Nadam(), 1e-2
+    assert n % 4 == 0
+    f = Flat(n, opt, stack.params.cpu().numpy())
+    f.lr.fill_(lr)
+    rng = np.random.default_rng(9)
+    for _ in range(3):
+        g = torch.from_numpy((rng.standard_normal(n) * 10.0 ** rng.uniform(-4, 0, n)).astype(np.float32)).to("cuda")
+        stack.grads.copy_(g)
+        f.g[:n] = g
+        stack.optimizer_step(opt, lr=lr)
+        assert f.step() == 0 and f.advance() == 0
+    torch.cuda.synchronize()
+    assert torch.equal(stack.params, f.w[:n]) and torch.equal(stack.adam_m, f.slots[0][:n]) and torch.equal(stack.adam_v, f.slots[1][:n])
+    assert int(stack.t_dev.item()) == int(f.t.item()) == 3
+    assert torch.equal(stack.opt_scalar, f.P) and float(f.P.item()) != 1.0
+    assert f.canaries_intact() and stack.opt_s2 is None
+
+
+def test_capture_step_graph_refuses_an_optimizer_outside_the_tail():
+    from dib_amd import optimizers as O
+    eng = _engine()
+    x, y = eng.to_device(np.zeros((16, 4), dtype=np.float32)), eng.to_device(np.zeros((16, 1), dtype=np.float32))
+    eng.enable_step_counter(0)
+    torch.cuda.synchronize()
+    n0 = eng.lib.dib_launch_count()
+    for opt in (O.RMSprop(), O.build(O.Adam, clipnorm=1.0)):
+        with pytest.raises(ValueError):
+            eng.capture_step_graph(x, y, 16, "bce_logits", 1.0 / 16, 0, True, optimizer=opt)
+    assert eng.lib.dib_launch_count() == n0 and 16 not in eng._ws_pinned

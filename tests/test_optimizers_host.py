@@ -52,6 +52,35 @@ def test_sgd_keeps_its_momentum_and_adam_its_amsgrad():
     assert optimizers.SGD().native and optimizers.Adam().native and optimizers.SGD(momentum=0.0).native
 
 
+def test_as_optimizer_maps_the_legacy_tuples_once_and_refuses_the_rest():
+    a = optimizers.as_optimizer(("adam", 0.8, 0.99, 1e-6))
+    assert type(a) is optimizers.Adam and (a.beta_1, a.beta_2, a.epsilon) == (0.8, 0.99, 1e-6) and a.rides_in_tail
+    assert optimizers.as_optimizer(("adam", 0.8, 0.99, 1e-6)) is a            # an equal tuple: the identical object
+    assert optimizers.as_optimizer(("adam", 0.9, 0.999, 1e-7)) is not a
+    s = optimizers.as_optimizer(("sgd",))
+    assert type(s) is optimizers.SGD and s.momentum == 0.0 and optimizers.as_optimizer(("sgd",)) is s
+    for opt in (a, optimizers.RMSprop(), optimizers.build(optimizers.Adam, clipnorm=1.0)):
+        assert optimizers.as_optimizer(opt) is opt
+    for bad in (("opt", optimizers.RMSprop()), ("adam",), ("adam", 0.9, 0.999), ("adam", 0.9, 0.999, [1e-7]), ("sgd", 0.9), ("rmsprop",),
+                (), "adam", None, 3, ["sgd"]):
+        with pytest.raises(ValueError):
+            optimizers.as_optimizer(bad)
+
+
+def test_rides_in_tail_is_plain_adam_and_plain_sgd_without_a_clip():
+    O = optimizers
+    for opt in (O.SGD(momentum=0.9), O.Adam(amsgrad=True), O.RMSprop(), O.Adagrad(), O.Adadelta(), O.Adamax(), O.Nadam()):
+        assert not opt.native and not opt.rides_in_tail
+    for cls in (O.Adam, O.SGD):
+        assert cls().rides_in_tail and cls(3e-4).rides_in_tail
+        assert O.build(cls, decay=0.1).rides_in_tail                          # a learning-rate setting is not a clip
+        for setting in ("clipnorm", "clipvalue", "global_clipnorm"):
+            opt = O.build(cls, **{setting: 1.0})
+            assert opt.native and not opt.rides_in_tail
+            setattr(opt, setting, None)
+            assert opt.rides_in_tail
+
+
 @pytest.mark.parametrize("name", ["ftrl", "adamw", "adafactor", "lion", "", None, 3])
 def test_unknown_names_are_refused_with_the_supported_set(name):
     with pytest.raises(ValueError) as e:

@@ -91,11 +91,10 @@ def kernels(args):
 
 def _steps(eng, x, y, B, opt, with_validation, pairs, repeats):
     import torch
-    tup = ("opt", opt) if (not opt.native or opt.clip() is not None) else ("adam", opt.beta_1, opt.beta_2, opt.epsilon)
 
     def pair(k):
         eng.apply_lr(opt)   # what fit does ahead of every step: nothing for an unchanged constant, one launch for a schedule
-        eng.train_step(x, y, None, 0, B, 1, k, "bce_logits", optimizer=tup)
+        eng.train_step(x, y, None, 0, B, 1, k, "bce_logits", optimizer=opt)
         if with_validation:
             eng.eval_step(x, y, None, 0, B, 1, (1 << 31) + k, "bce_logits", metrics_acc=eng.metrics_acc_val)
 

@@ -136,11 +136,11 @@ def model_steps(args, F, B, enc, integ, rule_name, with_validation, pairs):
     rec = {"features": F, "batch": B, "parameters": eng.n_params}
     # interleaved A / B / A: drift of the box shows as a difference between the two Adam entries
     opt = O.get(rule_name)
-    rec["adam"] = _steps(eng, x, y, B, ("adam", 0.9, 0.999, 1e-7), with_validation, pairs, args.repeats)
+    rec["adam"] = _steps(eng, x, y, B, O.Adam(), with_validation, pairs, args.repeats)
     eng.set_optimizer(opt)
-    rec[rule_name] = _steps(eng, x, y, B, ("opt", opt), with_validation, pairs, args.repeats)
+    rec[rule_name] = _steps(eng, x, y, B, opt, with_validation, pairs, args.repeats)
     eng.set_optimizer(O.Adam())
-    rec["adam_again"] = _steps(eng, x, y, B, ("adam", 0.9, 0.999, 1e-7), with_validation, pairs, args.repeats)
+    rec["adam_again"] = _steps(eng, x, y, B, O.Adam(), with_validation, pairs, args.repeats)
     rec["extra_us"] = rec[rule_name]["median_us"] - 0.5 * (rec["adam"]["median_us"] + rec["adam_again"]["median_us"])
     rec["extra_launches"] = rec[rule_name]["launches"] - rec["adam"]["launches"]
     del eng
