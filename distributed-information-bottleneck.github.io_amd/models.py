@@ -16,6 +16,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
+from . import _fit
 from . import losses as _losses
 from . import optimizers as _optimizers
 
@@ -151,6 +152,8 @@ class DistributedIBNet:
         # last encoder layer, each issued as soon as it is final (default); 2 = integration / encoder bank; 1 = one all-reduce
         self.dp_small_batch_rows = 1024   # per-rank batches up to this many rows use ONE gradient bucket (see fit)
         self.validation_merge_rows = 1024  # fit: full validation batches are evaluated together up to this many rows (0: one by one)
+        self.syncs_per_epoch = 1   # fit: 2 = A/B switch, round 5's order (the training sums read before the validation pass)
+        self._metric = None   # compile: (History key, DIB_METRIC_* name, square root at the end of the epoch)
         self.dp_buckets = int(os.environ.get("DIB_DP_BUCKETS", "3"))
         if self.dp_buckets not in (1, 2, 3):
             raise ValueError(f"DIB_DP_BUCKETS={self.dp_buckets}: 1, 2 or 3")
@@ -289,18 +292,9 @@ class DistributedIBNet:
             self._flat_leaf = eng.params.detach().requires_grad_(True)
         return self._flat_leaf
 
-    @staticmethod
-    def _device_input(eng, x):
-        """fit / evaluate / predict inputs: a float32 tensor already on the engine's device as the row-major matrix the kernels
-        read - itself when it is one, no trip through the host - or None for anything else (the NumPy path)"""
-        if not (isinstance(x, torch.Tensor) and x.device == eng.device and x.dtype == torch.float32):
-            return None
-        x = x.detach()
-        return (x.view(-1, 1) if x.dim() == 1 else x).contiguous()
-
     def predict(self, x, batch_size=None, verbose=0):
         eng = self._ensure_engine()
-        xd = self._device_input(eng, x)
+        xd = _fit.device_matrix(eng, x)
         if xd is None:
             xd = eng.to_device(x)
         n = xd.shape[0]
@@ -402,7 +396,7 @@ class DistributedIBNet:
     def _loss_arg(self):
         """what the engine's train_step / eval_step take: the kind's name for the reference's own kinds with today's 'accuracy'
         (dib_loss_fwd_bwd, the fused one-unit head), else the loss's descriptor with the metric (include/dib_losses.h)"""
-        loss, metric = self.loss, (self._metric[1] if getattr(self, "_metric", None) else None)
+        loss, metric = self.loss, (self._metric[1] if self._metric else None)
         if not hasattr(loss, "descriptor"):
             return loss.kind   # a foreign object with a `kind`
         if loss.legacy and metric in (None, loss.resolve_metric("accuracy")):
@@ -429,18 +423,6 @@ class DistributedIBNet:
             return dist, dist.get_rank(), dist.get_world_size()
         return None, 0, 1
 
-    def _set_lr(self, eng):
-        """the next step's learning rate on the device: a constant (free when unchanged), `decay` or a schedule (HipEngine.apply_lr)"""
-        opt = self.optimizer
-        if opt.lr_schedule() is None:
-            eng.set_lr(opt.learning_rate)
-        else:
-            eng.apply_lr(opt)
-
-    def _optimizer_step(self, eng):
-        self._set_lr(eng)
-        eng.optimizer_step(self.optimizer)
-
     def _epoch_logs(self, acc: np.ndarray, nsteps: int, prefix: str) -> Dict[str, float]:
         """History accounting (reference models.py:115,121; train.py:169-172):
         loss = sample-weighted mean of (task + beta*sum KL); add_metric scalars (KL{f}, beta) =
@@ -449,7 +431,7 @@ class DistributedIBNet:
         rows = max(acc[F + 2], 1.0)
         logs = {prefix + "loss": acc[F] / rows}
         if self.metrics_names:
-            key, _, root = getattr(self, "_metric", None) or ("accuracy", "accuracy", False)
+            key, _, root = self._metric or ("accuracy", "accuracy", False)
             # every metric is a sample-weighted mean of per-row values; root_mean_squared_error accumulates the squared errors
             # and takes the root here, at the end of the epoch (Keras' RootMeanSquaredError.result)
             logs[prefix + key] = math.sqrt(acc[F + 1] / rows) if root else acc[F + 1] / rows
@@ -481,42 +463,15 @@ class DistributedIBNet:
         eng = self._ensure_engine()
         dist, rank, world = self._dist()
         F = self.number_features
-        xd = self._device_input(eng, x)   # a table already on the device (tabular.TabularPreprocessor) is used where it lies
-        x_np = xd if xd is not None else np.asarray(x, dtype=np.float32)
-        if x_np.ndim == 1:
-            x_np = x_np[:, None]
-        y_np = np.asarray(y, dtype=np.float32)
-        if y_np.ndim == 1:
-            y_np = y_np[:, None]
-        assert x_np.shape[-1] == int(np.sum(self.feature_dimensionalities)), "input width != sum(feature dims)"
-        n = x_np.shape[0]
-        bs = int(batch_size or 32)
-        xd, yd = xd if xd is not None else eng.to_device(x_np), eng.to_device(y_np)
+        xd, y_np = _fit.device_rows(eng, x), _fit.host_rows(y)
+        assert xd.shape[-1] == int(np.sum(self.feature_dimensionalities)), "input width != sum(feature dims)"
+        yd = eng.to_device(y_np)
+        n, bs = xd.shape[0], int(batch_size or 32)
+        xvd = yvd = yv_np = None
         if validation_data is not None:
-            xvd = self._device_input(eng, validation_data[0])
-            xv_np = xvd if xvd is not None else np.asarray(validation_data[0], dtype=np.float32)
-            yv_np = np.asarray(validation_data[1], dtype=np.float32)
-            if xv_np.ndim == 1:
-                xv_np = xv_np[:, None]
-            if yv_np.ndim == 1:
-                yv_np = yv_np[:, None]
-            xvd, yvd = xvd if xvd is not None else eng.to_device(xv_np), eng.to_device(yv_np)
-        track = None
-        if track_information is not None:
-            track = dict(track_information)
-            unknown = set(track) - {"x", "every", "evaluation_batch_size", "number_evaluation_batches"}
-            if unknown:
-                raise ValueError(f"track_information: unknown keys {sorted(unknown)}")
-            if track.get("x") is not None:
-                xt = np.asarray(track["x"], dtype=np.float32)
-                track["x"] = eng.to_device(xt[:, None] if xt.ndim == 1 else xt)
-            elif validation_data is not None:
-                track["x"] = xvd
-            else:
-                raise ValueError("track_information needs inputs: give it `x` or fit(validation_data=...)")
-            track["every"] = int(track.get("every", 1))
-            if track["every"] < 1:
-                raise ValueError("track_information['every'] must be a positive number of epochs")
+            xvd, yv_np = _fit.device_rows(eng, validation_data[0]), _fit.host_rows(validation_data[1])
+            yvd = eng.to_device(yv_np)
+        track = _fit.parse_track_information(eng, track_information, xvd)
         cbs = list(callbacks or [])
         for cb in cbs:
             cb.set_model(self) if hasattr(cb, "set_model") else setattr(cb, "model", self)
@@ -533,162 +488,39 @@ class DistributedIBNet:
         for cb in cbs:
             if hasattr(cb, "on_train_begin"):
                 cb.on_train_begin()
-
-        def reduce_metrics(acc_np):
-            if dist is None:
-                return acc_np
-            t = torch.from_numpy(acc_np.copy()).to(eng.metrics_acc.device)
-            dist.all_reduce(t)
-            return t.cpu().numpy()
-
-        # Optional hipGraph replay of the whole step (DIB_ENABLE_GRAPHS=1; needs the device-resident noise step counter;
-        # single-process only).  Bit-identical to the eager launch sequence (tests).  OFF by default: measured on MI355X
-        # for the reference's default Boolean-circuit run (B = 128, ~30 launches/step) the replay is ~8 % SLOWER than
-        # eager (4.09 vs 3.76 ms/epoch, tools/small_batch_bench.py) - the step is bound by the latency of its dependent
-        # kernels, not by launch overhead.
-        n_full = n // bs
-        if hasattr(eng, "set_optimizer"):
-            eng.set_optimizer(self.optimizer)   # a change of rule re-initialises the optimizer state; the same rule: nothing
-        elif not self.optimizer.native:
-            raise ValueError(f"optimizer {self.optimizer.name!r} needs the HIP engine (include/dib_optimizers.h)")
-        if not hasattr(eng, "apply_lr") and (self.optimizer.clip() is not None or self.optimizer.lr_schedule() is not None):
-            raise ValueError("gradient clipping, decay and learning-rate schedules need the HIP engine (include/dib_grad_transform.h)")
-        # (the rules of include/dib_optimizers.h and every step behind a gradient transform always run eagerly: their step is not
-        # part of capture_step_graph; a schedule alone keeps the captured step - its one-thread launch goes ahead of each replay)
-        use_graphs = (dist is None and hasattr(eng, "capture_step_graph") and bs <= 8192 and n_full * epochs >= 64
-                      and self.optimizer.rides_in_tail and os.environ.get("DIB_ENABLE_GRAPHS", "0") == "1")
+        can_capture = _fit.bind_optimizer(eng, self.optimizer)
         graphs = {}
-        if use_graphs:
-            eng.enable_step_counter(self._step)
-            self._set_lr(eng)
-            graphs["train"] = eng.capture_step_graph(xd, yd, bs, kind, 1.0 / bs, self.noise_seed, True, self.optimizer)
-            eng.set_step_counter(self._step)
-        elif getattr(eng, "step_dev", None) is not None:
-            eng.set_step_counter(self._step)
-
-        def epoch_order(epoch):
-            """row order of `epoch` on the device (int32): Keras reshuffles every epoch; seeded by (shuffle_seed, epoch)"""
-            order = (np.random.default_rng([self.shuffle_seed, epoch]).permutation(n) if shuffle else np.arange(n)).astype(np.int32)
-            return eng.to_device(order, dtype=torch.int32)
-
+        step = _fit.choose_step(self, eng, xd, yd, bs, epochs, kind, dist, rank, world, can_capture, graphs)
+        nsteps = len(range(0, n, bs))   # every epoch: one step per batch, the partial last one included
         next_order = None
         try:
             for epoch in range(initial_epoch, epochs):
                 for cb in cbs:
                     cb.on_epoch_begin(epoch)
                 eng.set_beta(float(self.beta.value()))
-                order_dev = next_order if next_order is not None else epoch_order(epoch)
+                order_dev = next_order if next_order is not None else _fit.epoch_order(eng, n, shuffle, self.shuffle_seed, epoch)
                 next_order = None
-                nsteps = 0
                 for s0 in range(0, n, bs):
-                    gb = min(bs, n - s0)  # last partial batch is kept (Keras)
-                    if use_graphs and gb == bs:
-                        g, stage = graphs["train"]
-                        self._set_lr(eng)
-                        stage.copy_(order_dev[s0: s0 + bs])
-                        g.replay()  # fwd + loss + bwd + optimizer + metrics + step-counter bump
-                        self._step += 1
-                        nsteps += 1
-                        continue
-                    lo = (gb * rank) // world
-                    hi = (gb * (rank + 1)) // world
-                    # Every rank issues the SAME collectives every step, rows or no rows (a tail batch with fewer rows than
-                    # ranks leaves some ranks empty: they contribute zeros).  Gradient buckets of the layer-major flat buffer
-                    # (DESIGN 6), each all-reduced (RCCL, async) as soon as it is final:
-                    #   1 integration network   - under the whole encoder-bank backward
-                    #   2 encoder front layers  - under the last encoder layer's weight gradient      (dp_buckets == 3)
-                    #   3 last encoder layer    - the only exposed one                                (dp_buckets == 3)
-                    #   0 = 2 + 3 as one bucket after the backward                                    (dp_buckets == 2)
-                    pending = []
-                    nb = self.dp_buckets if dist is not None else 1
-                    if nb > 1 and gb // world <= self.dp_small_batch_rows:
-                        # small per-rank batches (<= 1024 rows: a handful of kernels per step, one grouped launch for every weight
-                        # gradient): the backward is a handful of launches with nothing to hide an all-reduce under - one
-                        # bucket after it, and the launches (hence the bits) of the single-process step.  Decided from the
-                        # GLOBAL batch: identical on every rank.
-                        nb = 1
-                    issue = lambda g: pending.append(dist.all_reduce(g, async_op=True))
-                    if dist is None:
-                        # one process: the step's LAST launch reduces the gradient partials, sums the KL / loss partials,
-                        # accumulates the History metrics and applies the optimizer (csrc/dib_tail.h) - or the engine steps an
-                        # optimizer that does not ride there right behind it
-                        self._set_lr(eng)
-                        eng.train_step(xd, yd, order_dev[s0: s0 + gb], 0, gb, self.noise_seed, self._step, kind,
-                                       inv_global_batch=1.0 / gb, optimizer=self.optimizer)
-                        self._step += 1
-                        nsteps += 1
-                        if getattr(eng, "step_dev", None) is not None:
-                            eng.set_step_counter(self._step)
-                        continue
-                    if hi > lo:
-                        eng.train_step(xd, yd, order_dev[s0 + lo: s0 + hi], 0, hi - lo, self.noise_seed, self._step, kind,
-                                       inv_global_batch=1.0 / gb, on_integration_grads_ready=issue if nb >= 2 else None,
-                                       **(dict(on_encoder_front_grads_ready=issue) if nb == 3 else {}))
-                    else:
-                        eng.grads.zero_()
-                        for part in ((1,) if nb == 2 else (1, 2) if nb == 3 else ()):
-                            off, cnt = eng.part_range(part)
-                            issue(eng.grads[off: off + cnt])
-                    if nb >= 2:
-                        off, cnt = eng.part_range(3 if nb == 3 else 0)
-                        issue(eng.grads[off: off + cnt])
-                        # each bucket is stepped as soon as ITS all-reduce has landed: buckets 1 (and 2) are updated on
-                        # the compute stream while the last bucket is still on the wire; every launch reads the same
-                        # Adam step count, the last one advances it
-                        self._set_lr(eng)
-                        parts = (1, 2, 3) if nb == 3 else (1, 0)
-                        for k, (w, part) in enumerate(zip(pending, parts)):
-                            w.wait()
-                            eng.optimizer_step_part(max(hi - lo, 1), part, self.optimizer, bump=k == len(parts) - 1)
-                    else:
-                        dist.all_reduce(eng.grads)
-                        self._optimizer_step(eng)
-                    self._step += 1
-                    nsteps += 1
-                    if getattr(eng, "step_dev", None) is not None:
-                        eng.set_step_counter(self._step)  # eager step under the device counter: keep it in sync
+                    step(order_dev, s0, min(bs, n - s0))  # last partial batch is kept (Keras)
                 # host work under the device's queue: the next epoch's permutation (12 ms of numpy for 2^20 rows - with it at
                 # the top of the epoch the device idled 7 % of a config-3 epoch, bench.py extra.fit_surface) and its upload are
                 # done while this epoch's steps are still executing; the read-back below is the epoch's only synchronisation
                 if epoch + 1 < epochs and not self.stop_training:
-                    next_order = epoch_order(epoch + 1)
+                    next_order = _fit.epoch_order(eng, n, shuffle, self.shuffle_seed, epoch + 1)
                 # ONE synchronisation per epoch: the validation pass is enqueued right behind the training steps - its History
                 # sums go to an accumulator of their own - and both are read back together (round 5 read the training sums
                 # first: the device idled through that round trip and the host work behind it, every epoch)
+                early = eng.read_metrics_pair()[0] if self.syncs_per_epoch == 2 else None
                 vsteps = 0
-                early = None
-                if getattr(self, "syncs_per_epoch", 1) == 2:   # A/B switch: round 5's order (training sums read before the validation pass)
-                    early = eng.read_metrics_pair()[0]
                 if validation_data is not None:
-                    nv = xvd.shape[0]
-                    if getattr(eng, "step_dev", None) is not None:
-                        eng.set_step_counter((1 << 31) + epoch)  # validation noise stream, same key as the eager path
-                    # Validation batches do not depend on each other - no state changes between them, one noise key per epoch
-                    # (rows keyed by their dataset index) - and every History quantity is linear in per-row sums: k full
-                    # batches are evaluated as ONE launch set of k * bs rows with the per-batch 1 / bs scaling and counted as k
-                    # steps.  Same per-row numbers, sums in another order (fp32 rounding).  At the reference's default (8
-                    # validation batches of 128 rows per epoch, train.py:30-34) that is 3 launches per epoch instead of 24.
-                    kmerge = max(1, self.validation_merge_rows // bs) if world == 1 else 1
-                    s0 = 0
-                    while s0 < nv:
-                        gb = min(bs, nv - s0)
-                        nb = min(kmerge, (nv - s0) // bs) if gb == bs else 1
-                        rows = gb * nb
-                        lo = (rows * rank) // world
-                        hi = (rows * (rank + 1)) // world
-                        if hi > lo:
-                            eng.eval_step(xvd, yvd, None, s0 + lo, hi - lo, self.noise_seed, (1 << 31) + epoch, kind,
-                                          inv_global_batch=1.0 / gb, metrics_acc=eng.metrics_acc_val)
-                        vsteps += nb
-                        s0 += rows
-                    if getattr(eng, "step_dev", None) is not None:
-                        eng.set_step_counter(self._step)
+                    _fit.sync_noise_step(eng, (1 << 31) + epoch)  # validation noise stream, same key as the eager path
+                    vsteps = _fit.evaluation_pass(eng, xvd, yvd, bs, kind, self.noise_seed, (1 << 31) + epoch,
+                                                  self.validation_merge_rows, rank, world, eng.metrics_acc_val)
+                    _fit.sync_noise_step(eng, self._step)
                 train_sums, val_sums = eng.read_metrics_pair()
-                if early is not None:
-                    train_sums = early
-                logs = self._epoch_logs(reduce_metrics(train_sums), nsteps, "")
+                logs = self._epoch_logs(_fit.reduce_metrics(eng, dist, train_sums if early is None else early), nsteps, "")
                 if validation_data is not None:
-                    logs.update(self._epoch_logs(reduce_metrics(val_sums), vsteps, "val_"))
+                    logs.update(self._epoch_logs(_fit.reduce_metrics(eng, dist, val_sums), vsteps, "val_"))
                 for k, v in logs.items():
                     hist.history.setdefault(k, []).append(float(v))
                 hist.epoch.append(epoch)
@@ -721,25 +553,14 @@ class DistributedIBNet:
         eng = self._ensure_engine()
         if self.loss is None:
             raise RuntimeError("call compile() before evaluate()")
-        xd = self._device_input(eng, x)
-        if xd is None:
-            xd = eng.to_device(np.asarray(x, dtype=np.float32))
-        y_np = np.asarray(y, dtype=np.float32)
-        y_np = y_np[:, None] if y_np.ndim == 1 else y_np
+        xd, y_np = _fit.device_rows(eng, x), _fit.host_rows(y)
         yd = eng.to_device(y_np)
         kind = self._loss_arg()
         self._check_labels(kind, y_np)
-        n, bs = xd.shape[0], int(batch_size or 32)
         eng.read_metrics()
-        steps = 0
         # full batches are evaluated together like fit's validation pass (same per-row numbers; see validation_merge_rows)
-        kmerge, s0 = max(1, self.validation_merge_rows // bs), 0
-        while s0 < n:
-            b = min(bs, n - s0)
-            nb = min(kmerge, (n - s0) // bs) if b == bs else 1
-            eng.eval_step(xd, yd, None, s0, b * nb, self.noise_seed, (1 << 31) - 1, kind, inv_global_batch=1.0 / b)
-            steps += nb
-            s0 += b * nb
+        steps = _fit.evaluation_pass(eng, xd, yd, int(batch_size or 32), kind, self.noise_seed, (1 << 31) - 1,
+                                     self.validation_merge_rows, 0, 1, None)
         return self._epoch_logs(eng.read_metrics(), steps, "")
 
 
