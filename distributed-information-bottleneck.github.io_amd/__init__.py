@@ -16,9 +16,10 @@ from .random_partition import RandomPartition  # noqa: F401
 from . import mi_characterization  # noqa: F401
 from . import tabular  # noqa: F401
 from .tabular import TabularPreprocessor  # noqa: F401
+from . import subset_information  # noqa: F401
 
 __all__ = ["DistributedIBNet", "DistributedIBModule", "InfoBottleneckAnnealingCallback", "SaveCompressionMatricesCallback",
            "InfoPerFeatureCallback", "PositionalEncoding", "Callback", "History", "models", "losses", "optimizers", "schedules", "data", "utils",
            "visualization", "ctw", "chaos_data", "set_transformer", "SetTransformerDIB", "measurement", "MeasurementIB",
            "circuit", "CircuitIB", "random_partition", "RandomPartition", "mi_characterization",
-           "tabular", "TabularPreprocessor"]
+           "tabular", "TabularPreprocessor", "subset_information"]

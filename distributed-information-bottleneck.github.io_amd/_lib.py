@@ -372,6 +372,15 @@ SIGNATURES_TABULAR = {
 }
 
 
+# include/dib_subsets.h: I(X_S;Y) of every subset of the features of a small discrete table
+SUBSET_MAX_BITS, SUBSET_MAX_CLASSES = 20, 16
+SIGNATURES_SUBSETS = {
+    "dib_subset_information_supported": (c_int, [c_int, c_int, c_int]),
+    "dib_subset_information_workspace_bytes": (c_int64, [c_int, c_int]),
+    "dib_subset_information": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+}
+
+
 class HostGradTable:
     """The host half of a variable table (include/dib_grad_transform.h): segments, the tile work-list, seg_tile0.  No GPU needed;
     `upload(device)` makes the dib_grad_table the launches take (engine.py, dense.py)."""
@@ -460,7 +469,7 @@ def _attach(lib):
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_ST.items()) + list(SIGNATURES_MEASURE.items()) \
             + list(SIGNATURES_CIRCUIT.items()) + list(SIGNATURES_PARTITION.items()) + list(SIGNATURES_MI_CHANNEL.items()) + list(SIGNATURES_MI_FEATURES.items()) \
             + list(SIGNATURES_COMPRESSION.items()) + list(SIGNATURES_OPTIMIZERS.items()) + list(SIGNATURES_LOSSES.items()) \
-            + list(SIGNATURES_GRAD_TRANSFORM.items()) + list(SIGNATURES_TABULAR.items()):
+            + list(SIGNATURES_GRAD_TRANSFORM.items()) + list(SIGNATURES_TABULAR.items()) + list(SIGNATURES_SUBSETS.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

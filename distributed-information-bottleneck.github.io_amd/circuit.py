@@ -104,6 +104,23 @@ def selected_subsets(info_in_parts, threshold: float = 0.1) -> list:
     return subsets
 
 
+def subset_comparison(info_in_parts, table, threshold: float = 0.1, backend: str = "device") -> list:
+    """cell 7's check of the subsets the DIB selected against the exhaustive ground truth: for every subset of
+    selected_subsets(info_in_parts, threshold), in that order, a dict with its gates, mask, size, information_bits = I(X_S;Y) on
+    the truth table ([rows, G + 1] 0/1, y last), rank among the subsets of its size (0 = the most informative: the colour
+    index) and best_bits_of_size.  One exhaustive evaluation (subset_information.subset_information) serves all of them."""
+    from . import subset_information as si
+    t = np.asarray(table)
+    info = si.subset_information(t[:, :-1], t[:, -1], backend=backend)
+    rows = []
+    for s in selected_subsets(info_in_parts, threshold):
+        gates = [int(g) for g in s]
+        mask = sum(1 << g for g in gates)
+        rows.append({"gates": gates, "mask": mask, "size": len(gates), "information_bits": float(info.bits[mask]),
+                     "rank": info.rank(mask), "best_bits_of_size": float(info.by_size(len(gates))[1][0])})
+    return rows
+
+
 def pack_truth_table(table) -> np.ndarray:
     """[2^G, G + 1] 0/1 rows -> uint32 words (bit g = input g, bit G = y); ValueError for any other table"""
     t = np.asarray(table)

@@ -115,6 +115,7 @@ struct Tuning {
   int int_cluster_min_weights = 65536;  // ... the network's hidden layers have at least this many weights (measured down to 4
                              // features x 32 -> 256 -> 256: 98 304)
   int wgrad_max_splits = 32; // most batch slabs of a layout's weight gradients (<= 32; read when a workspace is sized: set it first)
+  int subset_low_bits = 0;   // dib_subset_information: low key bits a workgroup folds in LDS (0: the most that fits; include/dib_subsets.h)
   int num_cus = 0;           // compute units the split rule prices rounds with; 0 = the current device's own count (device_cus)
 };
 // Process-wide and written ONLY by dib_set_tuning, which the header documents as a configuration call made while no other
@@ -192,6 +193,7 @@ static int* tuning_slot(const char* key) {
   if (!std::strcmp(key, "wgrad_recompute_h1")) return &t.wgrad_recompute_h1;
   if (!std::strcmp(key, "wgrad_max_splits")) return &t.wgrad_max_splits;
   if (!std::strcmp(key, "num_cus")) return &t.num_cus;
+  if (!std::strcmp(key, "subset_low_bits")) return &t.subset_low_bits;
   if (!std::strcmp(key, "attn_fwd_waves")) return &t.attn_fwd_waves;
   if (!std::strcmp(key, "int_cluster_short_exchange")) return &t.int_cluster_short_exchange;
   if (!std::strcmp(key, "int_cluster")) return &t.int_cluster;

@@ -67,6 +67,9 @@ def get_args(argv=None):
     p.add_argument('--pendulum_number_trajectories', type=int, default=0, help='0 = simulator default (1000)')
     p.add_argument('--boolean_random_circuit', type=_bool, default=False)
     p.add_argument('--boolean_number_input_gates', type=int, default=10)
+    p.add_argument('--subset_information', type=_bool, default=False,
+                   help='--dataset boolean_circuit: after fit, I(X_S;Y) of every subset of the input gates and their Shapley '
+                        'values (subset_information.npz + subset_information.png in --artifact_outdir); at most 20 gates')
     p.add_argument('--synthetic_rows', type=int, default=1 << 20)
     p.add_argument('--synthetic_features', type=int, default=64)
     p.add_argument('--table_path', type=str, default=None,
@@ -112,6 +115,30 @@ def save_compression_matrices_npz(saver, outdir):
              **{f'epoch{e}_feature{f}': m for (e, f), m in saver.matrices.items()})
 
 
+def check_subset_information_args(args):
+    """--subset_information goes with the Keras path on --dataset boolean_circuit and at most 20 input gates (2^20 subsets)"""
+    if not args.subset_information:
+        return
+    from .subset_information import MAX_BITS
+    if args.dataset != 'boolean_circuit' or args.infonce_loss:
+        raise ValueError("--subset_information True goes with --dataset boolean_circuit (and not with --infonce_loss)")
+    gates = args.boolean_number_input_gates if args.boolean_random_circuit else 10
+    if gates > MAX_BITS:
+        raise ValueError(f"--subset_information True: {gates} input gates have 2^{gates} subsets; the exhaustive table is "
+                         f"limited to {MAX_BITS} gates")
+
+
+def save_subset_information(dataset_dict, kl_series, loss_series, outdir, threshold=0.1):
+    """the exhaustive I(X_S;Y) of the circuit's truth table next to what the fit kept: the subsets of gates whose KL stayed above
+    `threshold` bits (circuit.selected_subsets) are the coloured points of the figure, the curve is (sum KL, H(Y) - loss)"""
+    from . import circuit, subset_information
+    info = subset_information.subset_information(dataset_dict['x_train'], dataset_dict['y_train'])
+    selected = [list(map(int, s)) for s in circuit.selected_subsets(kl_series, threshold)]
+    return subset_information.save_subset_information(
+        info, outdir, selected=selected, info_in_full=np.sum(kl_series, axis=-1),
+        predictive_information_out=info.entropy_y_bits - np.asarray(loss_series, dtype=np.float64), plot_start_ind=0)
+
+
 def main(argv=None):
     from . import data, models, optimizers, visualization
     args = get_args(argv)
@@ -123,6 +150,7 @@ def main(argv=None):
         dist.init_process_group("nccl")
     rank = dist.get_rank() if dist.is_initialized() else 0
     number_epochs = args.number_pretraining_epochs + args.number_annealing_epochs
+    check_subset_information_args(args)
     os.makedirs(args.artifact_outdir, exist_ok=True)
     dataset_dict = data.DATASETS[args.dataset](
         data_path=args.data_path, boolean_random_circuit=args.boolean_random_circuit,
@@ -208,6 +236,8 @@ def main(argv=None):
         visualization.save_distributed_info_plane(kl_series_validation, loss_series_validation, args.artifact_outdir)
         if saver is not None:
             save_compression_matrices_npz(saver, args.artifact_outdir)
+        if args.subset_information:
+            save_subset_information(dataset_dict, kl_series, loss_series, args.artifact_outdir)
         if history.information is not None:
             info = history.information
             np.savez(os.path.join(args.artifact_outdir, 'info_bounds.npz'), epochs=np.int64(info['epochs']),

@@ -311,6 +311,7 @@ int dib_step_tail(dib_layout* l, int batch, int part, int flags, float* params, 
  *   "int_cluster_short_exchange" (1) a cluster whose workgroups all report one XCC_ID exchanges through that XCD's L2 (no L2 write-back /
  *                           invalidate); 0: always the agent-scope protocol - what a cluster placed across XCDs takes (tests)
  *   "int_cluster_min_weights" (65536) the network's hidden layers hold at least this many weights
+ *   "subset_low_bits" (0)   dib_subset_information (dib_subsets.h): low key bits a workgroup folds in LDS; 0 = the most that fits
  * Returns DIB_E_ARG for an unknown key or a negative value. */
 int dib_set_tuning(const char* key, int value);
 int dib_get_tuning(const char* key, int* value);

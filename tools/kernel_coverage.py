@@ -103,6 +103,10 @@ ORACLE_TESTS = {
     "test_gpu_tabular.py": {
         "test_envelope_matches_the_float64_oracle", "test_crafted_values", "test_fixture_through_the_device_backend",
         "test_table_end_to_end_against_the_oracle_fit"},
+    "test_gpu_subset_information.py": {
+        "test_device_matches_the_host_backend_across_the_envelope", "test_multi_bit_features",
+        "test_every_fold_width_forced_through_its_tuning_key", "test_known_answers_are_exact",
+        "test_paper_circuit_matches_the_notebook_and_ranks_its_printed_sequence", "test_random_circuit_of_14_gates"},
 }
 # tests that demand the bits (or fp32 summation-order tolerance) of a path the tests above check against an oracle
 EQUIVALENCE_TESTS = {
@@ -154,6 +158,7 @@ EQUIVALENCE_TESTS = {
     "test_gpu_tabular.py": {
         "test_placement_does_not_change_the_bits", "test_graph_replay_has_the_eager_bits",
         "test_fit_on_a_device_tensor_equals_fit_on_numpy_bit_for_bit"},
+    "test_gpu_subset_information.py": {"test_chunks_and_placement_do_not_change_the_bits", "test_graph_replay_has_the_eager_bits"},
 }
 
 

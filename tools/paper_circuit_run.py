@@ -48,18 +48,11 @@ def group_order_violations(drop, slack=0):
     return bad
 
 
-def subset_information_bits(x, y):
-    """{bitmask of kept gates (bit i = gate i): I(X_S;Y) in bits} for all 2^10 subsets of the uniform truth table (the quantity
-    of Boolean_circuits.ipynb:425-434; the tests use the notebook's own numbers, tests/golden/subset_mi.npz)."""
-    bits = (np.asarray(x) > 0).astype(np.int64)
-    y = np.asarray(y).reshape(-1).astype(np.int64)
-    n, G = bits.shape
-    h = lambda c: float(-(c[c > 0] / n * np.log2(c[c > 0] / n)).sum())
-    out = {}
-    for mask in range(1 << G):
-        key = (bits[:, [i for i in range(G) if mask >> i & 1]] @ (1 << np.arange(bin(mask).count("1")))) if mask else np.zeros(n, np.int64)
-        out[mask] = h(np.bincount(key)) + h(np.bincount(y)) - h(np.bincount(key * 2 + y))
-    return out
+def subset_information_bits(x, y, backend="host"):
+    """I(X_S;Y) in bits of all 2^10 subsets of the uniform truth table, indexed by the bitmask of kept gates (bit i = gate i):
+    dib_amd.subset_information (the quantity of Boolean_circuits.ipynb:425-434; the tests use the notebook's own numbers,
+    tests/golden/subset_mi.npz).  backend "host" (float64 NumPy, what the CPU tests call) or "device" (one launch)."""
+    return dib_amd.subset_information.subset_information(x, y, backend=backend).bits
 
 
 def info_ceiling_excess(kl_bits, loss_bits, subset_info, entropy_y_bits, kept_threshold_bits=0.02):
@@ -78,7 +71,7 @@ def info_ceiling_excess(kl_bits, loss_bits, subset_info, entropy_y_bits, kept_th
 if __name__ == "__main__":
     import time
     _d = dib_amd.data.fetch_boolean_circuit()
-    _info = subset_information_bits(_d["x_train"], _d["y_train"])
+    _info = subset_information_bits(_d["x_train"], _d["y_train"], backend="device")
     # (beta_start = 1e-3, the notebook's value for ITS encoders - two trainable scalars per gate that start informative, mu = +-1 and
     # logvar = -3 - is too strong a bottleneck for MLP encoders that start uninformative: the XOR pair {7, 8} is priced out
     # before the integration network has learnt to use it (accuracy stays at 0.89, profiles/r04p_paper_circuit.txt); with

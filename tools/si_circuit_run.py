@@ -3,13 +3,13 @@ Y = AND(XOR(AND(x2,x0), x3), x1); Shapley values [0.096, 0.377, 0.096, 0.242]; H
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
 import dib_amd
-import dib_oracle as orc
+from dib_amd import circuit, subset_information
 
 
 def run(epochs_pre=100, epochs_anneal=500, seed=0):
-    x, y = orc.boolean_circuit_truth_table([0, 1, 2, 3, [0, 2, 0], [2, 4, 3], [0, 5, 1]], 4)
+    table = circuit.truth_table(circuit.SI_CIRCUITS[2])
+    x, y = 2 * table[:, :4] - 1, table[:, -1]
     x = np.tile(x, (8, 1)).astype(np.float32)
     y = np.tile(y, 8).astype(np.float32)
     m = dib_amd.DistributedIBNet([1, 1, 1, 1], [32, 32], [64, 64], 1, feature_embedding_dimension=8, noise_seed=seed,
@@ -29,3 +29,6 @@ if __name__ == "__main__":
     for e in (0, 50, 99, 150, 250, 350, 450, 520, 560, 599):
         print(e, f"beta={beta[e]:.4f}", "KL bits", np.round(kl[e], 3), f"loss={loss[e]:.3f} acc={acc[e]:.3f}")
     print("integrated KL over annealing", np.round(kl[100:].sum(0), 1))
+    _t = circuit.truth_table(circuit.SI_CIRCUITS[2])
+    _info = subset_information.subset_information(_t[:, :4], _t[:, -1])
+    print("Shapley values (bits)", np.round(_info.shapley_values(), 3), "H(Y)", round(_info.entropy_y_bits, 3))
