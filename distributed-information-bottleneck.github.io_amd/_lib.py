@@ -381,6 +381,25 @@ SIGNATURES_SUBSETS = {
 }
 
 
+# include/dib_ctw_device.h: the CTW entropy-rate estimator built level by level on the device
+CTW_DEVICE_MAX_ALPHABET, CTW_DEVICE_MAX_SYMBOLS = 16, 2 ** 31 - 1
+CTW_DEVICE_DEEP, CTW_DEVICE_OVERFLOW, CTW_DEVICE_BAD_SYMBOL = 1, 2, 4
+
+
+class CtwDeviceInfo(ctypes.Structure):
+    """dib_ctw_device_info"""
+    _fields_ = [("levels", c_int32), ("reserved", c_int32), ("element_steps", c_int64), ("big_nodes", c_int64),
+                ("level_seconds", ctypes.c_double), ("mix_seconds", ctypes.c_double)]
+
+
+SIGNATURES_CTW_DEVICE = {
+    "dib_ctw_device_supported": (c_int, [c_int, c_int64, c_int]),
+    "dib_ctw_device_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int64]),
+    "dib_ctw_device_estimate": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_int64, POINTER(CtwDeviceInfo), c_void_p]),
+}
+
+
 class HostGradTable:
     """The host half of a variable table (include/dib_grad_transform.h): segments, the tile work-list, seg_tile0.  No GPU needed;
     `upload(device)` makes the dib_grad_table the launches take (engine.py, dense.py)."""
@@ -469,7 +488,8 @@ def _attach(lib):
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_ST.items()) + list(SIGNATURES_MEASURE.items()) \
             + list(SIGNATURES_CIRCUIT.items()) + list(SIGNATURES_PARTITION.items()) + list(SIGNATURES_MI_CHANNEL.items()) + list(SIGNATURES_MI_FEATURES.items()) \
             + list(SIGNATURES_COMPRESSION.items()) + list(SIGNATURES_OPTIMIZERS.items()) + list(SIGNATURES_LOSSES.items()) \
-            + list(SIGNATURES_GRAD_TRANSFORM.items()) + list(SIGNATURES_TABULAR.items()) + list(SIGNATURES_SUBSETS.items()):
+            + list(SIGNATURES_GRAD_TRANSFORM.items()) + list(SIGNATURES_TABULAR.items()) + list(SIGNATURES_SUBSETS.items()) \
+            + list(SIGNATURES_CTW_DEVICE.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

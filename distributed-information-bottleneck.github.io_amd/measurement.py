@@ -307,32 +307,55 @@ class MeasurementIB:
 
 
 def entropy_rate_fit(symbolic_sequence, alphabet_size: int, number_data_points=None, number_rand_draws: int = 5, seed: int = 0,
-                     threads: int = 0) -> dict:
+                     threads: int = 0, ctw_backend: str = "host") -> dict:
     """CTW entropy rates of `number_rand_draws` random windows of each length (15 log-spaced lengths 2e3 .. 2e6 by default),
-    on `threads` host threads (0 = all), and the Schurmann-Grassberger fit h(N) = h + log2 N / N^g / |c|."""
+    on `threads` host threads (0 = all), and the Schurmann-Grassberger fit h(N) = h + log2 N / N^g / |c|.
+
+    ctw_backend "device": the same windows (the same rng.choice calls) are estimated by ctw.estimate_entropy_windows on the GPU;
+    symbolic_sequence may then be a CUDA uint8 tensor, which is used where it lies.  The result gains "ctw_details"."""
     from scipy import optimize
-    seq = np.asarray(symbolic_sequence)
+    if ctw_backend not in ("host", "device"):
+        raise ValueError(f"ctw_backend is 'host' or 'device'; got {ctw_backend!r}")
+    on_device = ctw_backend == "device" and torch.is_tensor(symbolic_sequence)
+    seq = symbolic_sequence.reshape(-1) if on_device else np.asarray(symbolic_sequence)
     if number_data_points is None:
         number_data_points = np.logspace(np.log10(2000), np.log10(2_000_000), 15, dtype=np.int32)
     number_data_points = np.asarray(number_data_points)
     rng = np.random.default_rng(seed)
-    windows = []
+    windows, starts, lengths = [], [], []
     for n in number_data_points:
         for _ in range(number_rand_draws):
             s = rng.choice(len(seq) - int(n))
-            windows.append(seq[s: s + int(n)])
-    rates = np.asarray(ctw.estimate_entropy_batch(windows, alphabet_size, threads=threads),
-                       dtype=np.float64).reshape(-1, number_rand_draws)
+            if ctw_backend == "host":
+                windows.append(seq[s: s + int(n)])
+            starts.append(int(s))
+            lengths.append(int(n))
+    extra = {}
+    if ctw_backend == "host":
+        rates = ctw.estimate_entropy_batch(windows, alphabet_size, threads=threads)
+    else:
+        rates, extra["ctw_details"] = ctw.estimate_entropy_windows(seq, starts, lengths, alphabet_size, backend="device",
+                                                                   return_details=True, threads=threads)
+    rates = np.asarray(rates, dtype=np.float64).reshape(-1, number_rand_draws)
     mean, err = rates.mean(1), rates.std(1)
     fit_vals, pcov = optimize.curve_fit(utils.entropy_rate_scaling_ansatz, number_data_points, mean, p0=[1, 0.5, 1], sigma=err)
     return {"number_data_points": number_data_points, "entropy_rate_values": rates, "entropy_rate": float(fit_vals[0]),
-            "entropy_rate_err": float(np.sqrt(np.diag(pcov))[0])}
+            "entropy_rate_err": float(np.sqrt(np.diag(pcov))[0]), **extra}
 
 
 def characterize_partition(symbolic_sequence, alphabet_size: int, number_data_points=None, number_rand_draws: int = 5,
-                           seed: int = 0, threads: Optional[int] = None) -> dict:
+                           seed: int = 0, threads: Optional[int] = None, ctw_backend: str = "host") -> dict:
     """cell 10 after the symbolisation: H(U) of one symbol and entropy_rate_fit of the sequence.  threads: CTW host threads
-    (None or 0 = all hardware threads)."""
-    seq = np.asarray(symbolic_sequence)
-    fit = entropy_rate_fit(seq, alphabet_size, number_data_points, number_rand_draws, seed, threads=int(threads or 0))
-    return {"entropy_single_timestep": float(utils.compute_entropy(seq)), **fit}
+    (None or 0 = all hardware threads).  ctw_backend: entropy_rate_fit's; a CUDA tensor of symbols stays on the device for the
+    windows (H(U) is taken from its histogram)."""
+    if ctw_backend == "device" and torch.is_tensor(symbolic_sequence):
+        seq = symbolic_sequence.reshape(-1)
+        c = torch.bincount(seq.to(torch.int64)).cpu().numpy()
+        c = c[c > 0]
+        h_u = float(-np.sum(c / c.sum() * np.log2(c / c.sum())))
+    else:
+        seq = np.asarray(symbolic_sequence)
+        h_u = float(utils.compute_entropy(seq))
+    fit = entropy_rate_fit(seq, alphabet_size, number_data_points, number_rand_draws, seed, threads=int(threads or 0),
+                           ctw_backend=ctw_backend)
+    return {"entropy_single_timestep": h_u, **fit}

@@ -4,7 +4,8 @@ evaluation trajectory is symbolised through it and the symbol sequence character
 
 Device path: one dib_partition_symbolize launch per chunk (include/dib_partition.h, csrc/dib_partition.h) reads the points
 (fp32 or fp64), runs the whole MLP, the argmax of |output| and the symbol histogram, and writes one byte per point.  The
-characterisation after it is host C++ (dib_amd.ctw) and the Schurmann-Grassberger fit of measurement.characterize_partition.
+characterisation after it is the CTW estimator (dib_amd.ctw: host C++ by default, ctw_backend="device" for the level build of
+csrc/dib_ctw_levels.h) and the Schurmann-Grassberger fit of measurement.characterize_partition.
 There is no CPU fallback: a network outside dib_partition_supported raises."""
 from __future__ import annotations
 
@@ -144,17 +145,21 @@ class RandomPartition:
                                                ctypes.c_void_p(counts.data_ptr()) if counts is not None else None, st),
               "dib_partition_symbolize")
 
-    def symbolize(self, data, chunk_size: int = 1 << 22, return_counts: bool = False):
-        """uint8 [n] symbols of the points data [n, d] (float32 or float64), and with return_counts the int64 [A] histogram.
-        Host arrays are copied to the device one chunk at a time; one launch per chunk, the counts accumulate on the device."""
+    def symbolize_device(self, data, chunk_size: int = 1 << 22, return_counts: bool = False):
+        """symbolize, the results left on the device: uint8 [n] tensor (and the int64 [A] histogram tensor)"""
         n = int(data.shape[0])
         sym = torch.empty(n, dtype=torch.uint8, device=self.device)
         counts = torch.zeros(self.A, dtype=torch.int64, device=self.device) if return_counts else None
         for c0 in range(0, n, int(chunk_size)):
             c1 = min(n, c0 + int(chunk_size))
             self._launch(self._input(data[c0:c1]), sym[c0:c1], None, counts)
-        s = sym.cpu().numpy()
-        return (s, counts.cpu().numpy()) if return_counts else s
+        return (sym, counts) if return_counts else sym
+
+    def symbolize(self, data, chunk_size: int = 1 << 22, return_counts: bool = False):
+        """uint8 [n] symbols of the points data [n, d] (float32 or float64), and with return_counts the int64 [A] histogram.
+        Host arrays are copied to the device one chunk at a time; one launch per chunk, the counts accumulate on the device."""
+        out = self.symbolize_device(data, chunk_size, return_counts)
+        return (out[0].cpu().numpy(), out[1].cpu().numpy()) if return_counts else out.cpu().numpy()
 
     def logits(self, data) -> np.ndarray:
         """float32 [n, A] outputs of the network (for inspection and tests)"""
@@ -166,28 +171,40 @@ class RandomPartition:
         return out.cpu().numpy()
 
     def characterize(self, data_or_symbols, number_data_points=None, number_rand_draws: int = 5, seed: int = 0,
-                     threads: Optional[int] = None) -> dict:
+                     threads: Optional[int] = None, ctw_backend: str = "host") -> dict:
         """H(U) from the kernel's symbol histogram (or of the given uint8 symbols) and the entropy rate from the CTW windows and
-        Schurmann-Grassberger fit of measurement.characterize_partition; threads: CTW host threads (default ctw_threads())."""
+        Schurmann-Grassberger fit of measurement.characterize_partition; threads: CTW host threads (default ctw_threads()).
+        ctw_backend "device": the symbols stay on the device between the symbolise kernel and the CTW level build (uint8
+        symbols given as a CUDA tensor are used where they lie); the result gains "ctw_details"."""
         arr = data_or_symbols
         if isinstance(arr, np.ndarray) and arr.dtype == np.uint8 and arr.ndim == 1:
             sym, counts = arr, np.bincount(arr, minlength=self.A)
+        elif ctw_backend == "device" and torch.is_tensor(arr) and arr.dtype == torch.uint8 and arr.dim() == 1:
+            sym = arr.to(self.device)
+            counts = torch.bincount(sym.to(torch.int64), minlength=self.A).cpu().numpy()
+        elif ctw_backend == "device":
+            sym, counts = self.symbolize_device(arr, return_counts=True)
+            counts = counts.cpu().numpy()
         else:
             sym, counts = self.symbolize(arr, return_counts=True)
         out = measurement.entropy_rate_fit(sym, self.A, number_data_points, number_rand_draws, seed,
-                                           threads=ctw_threads() if threads is None else threads)
+                                           threads=ctw_threads() if threads is None else threads, ctw_backend=ctw_backend)
         out["entropy_single_timestep"] = entropy_from_counts(counts)
         return out
 
 
 # ---- cell 7 ---------------------------------------------------------------------------------------------------------------
-def _symbolize_partition(weights, activation: str, trajectory, cache: dict):
-    """(symbols, counts) of the trajectory through one network; the trajectory is copied to the device once per survey"""
+def _symbolize_partition(weights, activation: str, trajectory, cache: dict, on_device: bool = False):
+    """(symbols, counts) of the trajectory through one network; the trajectory is copied to the device once per survey.
+    on_device: the symbols stay a device tensor (the counts come to the host either way)"""
     if "x" not in cache:
         cache["x"] = torch.from_numpy(np.ascontiguousarray(trajectory)).to("cuda")
     x = cache["x"]
     rp = RandomPartition(x.shape[1], weights[-1].shape[0], len(weights) // 2 - 1, activation, weights[0].shape[1],
                          weights=weights)
+    if on_device:
+        sym, counts = rp.symbolize_device(x, chunk_size=max(1, int(x.shape[0])), return_counts=True)
+        return sym, counts.cpu().numpy()
     return rp.symbolize(x, chunk_size=max(1, int(x.shape[0])), return_counts=True)
 
 
@@ -206,13 +223,17 @@ def random_partition_survey(trajectory, alphabet_sizes=(2, 4), layer_counts=(1, 
                             number_random_repeats: int = 1, seed: int = 0, entropy_threshold: float = 0.1,
                             number_data_points=None, number_rand_draws: int = 5, out_dir: Optional[str] = None,
                             save_point_assignments: bool = False, threads: Optional[int] = None,
-                            units_per_mlp_layer: int = 64) -> List[Dict]:
+                            units_per_mlp_layer: int = 64, ctw_backend: str = "host") -> List[Dict]:
     """Cell 7: for rand_iter, then A, then N, then the activation (the notebook's loop order), a random network of
     draw_weights(seed=partition_seed(...)) symbolises the whole trajectory; a partition with H(U) < entropy_threshold bits is
     skipped (no entropy rate, no file); otherwise its entropy rate comes from CTW windows (number_data_points: the 15 log-spaced
     lengths 2e3 .. 2e6 by default, number_rand_draws each) and the fit.  With out_dir, writes
     {N}layers_{act}_{A}alphabet_{iter}.npz with cell 7's keys (and the first 64 000 points and symbols with
-    save_point_assignments), which cell 8 reads back.  Returns one record per partition, skipped ones included."""
+    save_point_assignments), which cell 8 reads back.  Returns one record per partition, skipped ones included.
+    ctw_backend "device": the symbols go from the symbolise kernel to the CTW level build without leaving the device
+    (measurement.entropy_rate_fit); the same windows are drawn."""
+    if ctw_backend not in ("host", "device"):
+        raise ValueError(f"ctw_backend is 'host' or 'device'; got {ctw_backend!r}")
     traj = np.asarray(trajectory)
     if traj.ndim == 1:
         traj = traj[:, None]
@@ -231,7 +252,10 @@ def random_partition_survey(trajectory, alphabet_sizes=(2, 4), layer_counts=(1, 
                            "seed": ps}
                     t0 = time.perf_counter()
                     w = draw_weights(d, A, N, units_per_mlp_layer, seed=ps)
-                    sym, counts = _symbolize_partition(w, act, traj, cache)
+                    if ctw_backend == "device":
+                        sym, counts = _symbolize_partition(w, act, traj, cache, on_device=True)
+                    else:
+                        sym, counts = _symbolize_partition(w, act, traj, cache)
                     t1 = time.perf_counter()
                     h_u = entropy_from_counts(counts)
                     rec.update(entropy_single_timestep=h_u, counts=np.asarray(counts).tolist(), symbolize_s=t1 - t0)
@@ -239,7 +263,8 @@ def random_partition_survey(trajectory, alphabet_sizes=(2, 4), layer_counts=(1, 
                         rec.update(skipped=True, entropy_rate=None, entropy_rate_err=None, file=None)
                         records.append(rec)
                         continue
-                    fit = measurement.entropy_rate_fit(sym, A, number_data_points, number_rand_draws, ps, threads=th)
+                    fit = measurement.entropy_rate_fit(sym, A, number_data_points, number_rand_draws, ps, threads=th,
+                                                       ctw_backend=ctw_backend)
                     rec.update(skipped=False, entropy_rate=fit["entropy_rate"], entropy_rate_err=fit["entropy_rate_err"],
                                entropy_rate_values=fit["entropy_rate_values"], characterize_s=time.perf_counter() - t1,
                                file=None)
@@ -249,7 +274,7 @@ def random_partition_survey(trajectory, alphabet_sizes=(2, 4), layer_counts=(1, 
                                     entropy_rate=fit["entropy_rate"], entropy_rate_err=fit["entropy_rate_err"])
                         if save_point_assignments:
                             arrs["raw_data_points"] = traj[:64_000]
-                            arrs["symbolic_sequence"] = np.asarray(sym[:64_000])
+                            arrs["symbolic_sequence"] = np.asarray(sym[:64_000].cpu() if torch.is_tensor(sym) else sym[:64_000])
                         np.savez(f, **arrs)
                         rec["file"] = f
                     records.append(rec)

@@ -3,9 +3,11 @@
  * Replaces the reference's only native component, the Cython extension `ctw`
  * (reference chaos/ctw.pyx:2 `estimate_entropy(seq, alphabet_size)` -> chaos/cppctw.hpp:21 `ctw::cpp_ctw`
  *  -> chaos/cppctw.cpp:160-171 `estimate_entropy(const vector<char>&, char)`), which the chaos notebook calls
- * 75 times per partition.  Host C++ (the algorithm is a serial suffix-tree build - not a
- * GPU kernel): plain pointers and sizes, no Python / torch types, thread-safe (the reference keeps alphabet size and
- * beta in static members, chaos/cppctw.cpp:86-87, so it is not), and batchable across host threads.
+ * 75 times per partition.  Host C++: the reference's serial suffix-tree build, position by
+ * position (the same tree is built level by level on the device by include/dib_ctw_device.h, which falls back on
+ * this estimator where a context longer than 512 symbols repeats).  Plain pointers and sizes, no Python / torch
+ * types, thread-safe (the reference keeps alphabet size and beta in static members, chaos/cppctw.cpp:86-87, so it is
+ * not), and batchable across host threads.
  *
  * Results are bit-identical to the reference build on the same libm, including its float32 rounding of the final
  * rate (chaos/cppctw.cpp:101 returns `float`) and its MAX_DEPTH = 512 context cut-off (chaos/cppctw.cpp:13).

@@ -445,4 +445,6 @@ int dib_gemm(int mode, int M, int N, int K, const float* A, int lda, const float
 #ifdef __cplusplus
 }
 #endif
+/* the CTW entropy-rate estimator on the device (additions within ABI 7) */
+#include "dib_ctw_device.h"
 #endif /* DIB_HIP_H */

@@ -28,6 +28,8 @@ def main(argv=None):
     ap.add_argument("--eval-points", type=int, default=4_000_000)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--ctw_backend", default="host", choices=("host", "device"),
+                    help="where the CTW entropy rates are estimated (dib_amd.ctw.estimate_entropy_windows)")
     a = ap.parse_args(argv)
     import dib_amd
     from dib_amd import chaos_data
@@ -48,9 +50,9 @@ def main(argv=None):
     sym = m.symbolize(ev, number_averaging_logits=100, seed=a.seed)
     t_sym = time.time() - t0
     t0 = time.time()
-    ch = characterize_partition(sym, 2, number_rand_draws=5, seed=a.seed)
+    ch = characterize_partition(sym, 2, number_rand_draws=5, seed=a.seed, ctw_backend=a.ctw_backend)
     t_char = time.time() - t0
-    rec = {"system": a.system, "number_states": a.number_states, "alphabet_size": 2, "max_steps": a.steps,
+    rec = {"system": a.system, "number_states": a.number_states, "alphabet_size": 2, "max_steps": a.steps, "ctw_backend": a.ctw_backend,
            "steps_run": h["steps"], "reached_1_bit": stopped,
            "stopping_step": h["steps"] if stopped else None,
            "info_in_bits_last": info[-1] if info else None, "info_out_bits_last": float(h["info_out"][-1]) if h["info_out"] else None,

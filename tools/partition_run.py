@@ -26,6 +26,8 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--npz-dir", default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--ctw_backend", default="host", choices=("host", "device"),
+                    help="where the CTW entropy rates are estimated (dib_amd.ctw.estimate_entropy_windows)")
     a = ap.parse_args(argv)
     import torch
     from dib_amd import chaos_data
@@ -41,7 +43,8 @@ def main(argv=None):
         gen_s = time.perf_counter() - t0
         np.save(path, traj)
     t0 = time.perf_counter()
-    recs = rp.random_partition_survey(traj, number_random_repeats=a.repeats, seed=a.seed, out_dir=a.npz_dir)
+    recs = rp.random_partition_survey(traj, number_random_repeats=a.repeats, seed=a.seed, out_dir=a.npz_dir,
+                                      ctw_backend=a.ctw_backend)
     survey_s = time.perf_counter() - t0
     kept = [r for r in recs if not r["skipped"]]
     rates = [r["entropy_rate"] for r in kept]
@@ -49,7 +52,7 @@ def main(argv=None):
     out = {"what": "Chaos_experiments.ipynb cell 7 (Fig. 1): random-MLP partitions of the Ikeda map",
            "device": torch.cuda.get_device_name(0), "points": len(traj), "trajectory_seed": a.seed,
            "trajectory_generation_s": None if gen_s is None else round(gen_s, 1), "repeats": a.repeats, "survey_s": round(survey_s, 1),
-           "ctw_threads": rp.ctw_threads(), "h_ks": H_KS, "all_rates_below_h_ks_within_err": below,
+           "ctw_threads": rp.ctw_threads(), "ctw_backend": a.ctw_backend, "h_ks": H_KS, "all_rates_below_h_ks_within_err": below,
            "partitions": len(recs), "skipped": len(recs) - len(kept),
            "rate_min": min(rates) if rates else None, "rate_max": max(rates) if rates else None,
            "notebook_printed_rate_range": [0.266, 0.688],
