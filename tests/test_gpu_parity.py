@@ -170,7 +170,10 @@ def test_eps_matches_oracle_and_host_ref():
 def test_forward_backward_parity(name, B, path):
     """The architecture zoo x batch sizes x BOTH SIDES OF EVERY DISPATCH SWITCH (tests/_helpers.py dispatch_path) against the
     float64 oracle.  B = 2100 is beyond the row-tile regime for every layout (> 2048 rows): the fused-eligible entries then
-    run the persistent fused kernels over several 256-row tiles per workgroup on the default path too."""
+    run the persistent fused kernels on the default path too - 9 tiles of 256 rows, the last a tail of 52, on a grid of
+    min(9, 256 / F) = 9 workgroups per feature (every zoo entry has F <= 8), so each workgroup makes exactly ONE trip of its
+    tile loop.  The loop's later trips (tile += gridDim.x, the rotated prefetch, the accumulators carried across trips, a
+    tail tile that arrives as a second trip) are tests/test_gpu_fused_envelope.py's."""
     if B == 2100 and (name not in FUSED_ELIGIBLE or path == "large_batch"):
         pytest.skip("B = 2100 is the large-batch case of the fused-eligible entries (default == large_batch there)")
     if path == "cluster_tiles" and B not in (37, 300):
