@@ -8,7 +8,7 @@ from . import chaos_data, ctw, data, dense, infonce, losses, models, optimizers,
 from .models import (Callback, DistributedIBModule, DistributedIBNet, History, InfoBottleneckAnnealingCallback, InfoPerFeatureCallback,  # noqa: F401
                      PositionalEncoding, SaveCompressionMatricesCallback)
 from .set_transformer import SetTransformerDIB  # noqa: F401
-from .measurement import MeasurementIB  # noqa: F401
+from .measurement import MeasurementEnsemble, MeasurementIB  # noqa: F401
 from . import circuit  # noqa: F401
 from .circuit import CircuitIB  # noqa: F401
 from . import random_partition  # noqa: F401
@@ -20,6 +20,6 @@ from . import subset_information  # noqa: F401
 
 __all__ = ["DistributedIBNet", "DistributedIBModule", "InfoBottleneckAnnealingCallback", "SaveCompressionMatricesCallback",
            "InfoPerFeatureCallback", "PositionalEncoding", "Callback", "History", "models", "losses", "optimizers", "schedules", "data", "utils",
-           "visualization", "ctw", "chaos_data", "set_transformer", "SetTransformerDIB", "measurement", "MeasurementIB",
+           "visualization", "ctw", "chaos_data", "set_transformer", "SetTransformerDIB", "measurement", "MeasurementIB", "MeasurementEnsemble",
            "circuit", "CircuitIB", "random_partition", "RandomPartition", "mi_characterization",
            "tabular", "TabularPreprocessor", "subset_information"]

@@ -136,6 +136,9 @@ SIGNATURES = {
     "dib_infonce_workspace_bytes": (c_int64, [c_int]),
     "dib_infonce_fwd_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p]),
+    "dib_infonce_batched_workspace_bytes": (c_int64, [c_int, c_int]),
+    "dib_infonce_fwd_bwd_batched": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p]),
     "dib_positional_encoding": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dib_positional_encoding_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dib_mlp_small_supported": (c_int, [c_void_p, c_int]),
@@ -231,6 +234,12 @@ SIGNATURES_MEASURE = {
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dib_measure_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dib_measure_batched_workspace_bytes": (c_int64, [c_void_p, c_int, c_int]),
+    "dib_measure_fwd_batched": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_uint32, c_float, c_float,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dib_measure_bwd_batched": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_uint32, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p]),
     "dib_measure_symbolize": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "dib_measure_posenc_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
 }

@@ -97,4 +97,85 @@ int dib_infonce_fwd_bwd(const float* emb_x, const float* emb_y, int batch, int d
   return (int)hipGetLastError();
 }
 
+// ---- R independent problems [R][B][D] in the launches of one: the dot-product similarities on both routes above, the replica
+// as a grid index (csrc/dib_infonce_mfma.h, the batched kernels).  Replica r's workspace is `ince_batched_map(batch).stride` floats
+// on from replica r - 1's: S [B^2] | row / column block partials [4 ceil(B/32) B] | loss partials [ceil(2B/32)] | lse [2B] |
+// norms [2B] | arrival counter | slice partials of C . Other and of the row sums, sized as the single entry point sizes them
+// (the B^2 tables of the l1 / linf path, 7/8 of that workspace at B = 2048, are not needed here). ----
+struct InceBatchedMap { long long prow, pcol, lpart, lse, norms, stride; };
+static InceBatchedMap ince_batched_map(int batch) {
+  const long long B = batch, nb32 = cdiv(batch, 32);
+  InceBatchedMap m;
+  m.prow = B * B;
+  m.pcol = m.prow + 2 * nb32 * B;
+  m.lpart = m.pcol + 2 * nb32 * B;
+  m.lse = (m.lpart + cdiv(2 * batch, 32) + 3) / 4 * 4;
+  m.norms = m.lse + 2 * B;
+  m.stride = (m.norms + 2 * B + 64 + (4096ll + 16ll) * B + 3) / 4 * 4;
+  return m;
+}
+
+int64_t dib_infonce_batched_workspace_bytes(int replicas, int batch) {
+  if (batch <= 0 || replicas <= 0) return DIB_E_ARG;
+  return (int64_t)replicas * ince_batched_map(batch).stride * (int64_t)sizeof(float);
+}
+
+int dib_infonce_fwd_bwd_batched(const float* emb_x, const float* emb_y, int replicas, int batch, int dim, int similarity,
+                                float temperature, float* g_x, float* g_y, float* loss_out, void* ws, dib_stream_t stream) {
+  if (!emb_x || !emb_y || !loss_out || !ws || replicas <= 0 || batch <= 0 || dim <= 0 || temperature <= 0.f) return DIB_E_ARG;
+  if (!(similarity == 0 || similarity == 1 || similarity == 4) || dim > 256 || replicas > 32767) return DIB_E_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  const int R = replicas;
+  const bool grads = g_x && g_y;
+  const float inv_t = 1.0f / temperature;
+  const InceBatchedMap map = ince_batched_map(batch);
+  const long long stride = map.stride;   // a multiple of 4 floats
+  ProfScope ps(kProfOther, st);
+  if (batch <= DIB_INCE1_MAXB && dim <= 64 && knobs().infonce_one_launch) {
+    const dim3 grid(grads ? cdiv(batch, 64) : 1, grads ? 2 : 1, R);
+    const size_t lds = (size_t)DIB_INCE1_LDS_FLOATS * sizeof(float);
+#define DIB_INCE_ONE(KD)                                                                                                        \
+    launch_lds<&dib_infonce_batched_small_kernel<KD>>(grid, dim3(DIB_INCE1_THREADS), lds, st, emb_x, emb_y, batch, dim, inv_t,   \
+                                                      temperature, grads ? g_x : (float*)nullptr, grads ? g_y : (float*)nullptr, \
+                                                      loss_out)
+    return similarity == 0 ? DIB_INCE_ONE(0) : (similarity == 1 ? DIB_INCE_ONE(1) : DIB_INCE_ONE(4));
+#undef DIB_INCE_ONE
+  }
+  // replica 0's regions
+  float* S = (float*)ws;
+  float* lse = S + map.lse;
+  float* norms = S + map.norms;
+  const int nb32 = cdiv(batch, 32), t64 = cdiv(batch, 64);
+  float* prow = S + map.prow;
+  float* pcol = S + map.pcol;
+  unsigned* arrive = (unsigned*)(norms + 2ll * batch + 16);
+  float* Gp = norms + 2ll * batch + 64;
+  const int nsplit = t64 <= 4 ? 1 : std::max(1, std::min(std::min(t64, 8), cdiv(512, 2 * t64)));
+  float* Rp = Gp + 2ll * nsplit * batch * dim;
+  const int nacc = cdiv(dim, 64);
+  const size_t os_bytes = (size_t)64 * (64 * nacc + 4) * sizeof(float);
+#define DIB_INCE_SIM(KD) DIB_LAUNCH(dib_infonce_batched_sim_kernel<KD>, dim3(t64, t64, R), dim3(256), 0, st, emb_x, emb_y, batch, \
+                                    dim, inv_t, norms, S, prow, pcol, nb32, arrive, stride)
+  if (similarity == 0) DIB_INCE_SIM(0); else if (similarity == 1) DIB_INCE_SIM(1); else DIB_INCE_SIM(4);
+#undef DIB_INCE_SIM
+  float* lpart = S + map.lpart;
+  DIB_LAUNCH(dib_infonce_batched_lse_loss_kernel, dim3(cdiv(2 * batch, 32), R), dim3(256), 0, st, (const float*)prow,
+             (const float*)pcol, (const float*)S, batch, nb32, lse, arrive, lpart, loss_out, stride);
+  if (grads) {
+    const dim3 grid(t64, nsplit, 2 * R);
+#define DIB_INCE_GRAD(NA, KD) launch_lds<&dib_infonce_batched_grad_kernel<NA, KD>>(grid, dim3(256), os_bytes, st, emb_x, emb_y,    \
+                                                 (const float*)S, (const float*)lse, (const float*)norms, batch, dim, inv_t,    \
+                                                 temperature, nsplit, Gp, Rp, g_x, g_y, stride)
+#define DIB_INCE_GRAD_K(KD) (nacc == 1 ? DIB_INCE_GRAD(1, KD) : nacc == 2 ? DIB_INCE_GRAD(2, KD)                             \
+                                       : nacc == 3 ? DIB_INCE_GRAD(3, KD) : DIB_INCE_GRAD(4, KD))
+    if (int rc = similarity == 0 ? DIB_INCE_GRAD_K(0) : (similarity == 1 ? DIB_INCE_GRAD_K(1) : DIB_INCE_GRAD_K(4))) return rc;
+#undef DIB_INCE_GRAD_K
+#undef DIB_INCE_GRAD
+    if (nsplit > 1)
+      DIB_LAUNCH(dib_infonce_batched_grad_final_kernel, dim3(cdiv(2ll * batch * dim, 256), R), dim3(256), 0, st, emb_x, emb_y,
+                 (const float*)Gp, (const float*)Rp, batch, dim, similarity, nsplit, g_x, g_y, stride);
+  }
+  return (int)hipGetLastError();
+}
+
 }  // extern "C"

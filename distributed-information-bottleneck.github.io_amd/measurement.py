@@ -12,7 +12,11 @@ Device path of one training step (include/dib_measure.h, csrc/dib_measure.h; the
     dib_measure_bwd                              d soft symbols, softmax and VQ dgrad chain, d(mu | logvar) with the KL term
     VQ weight gradients, IB encoder backward     grouped GEMMs on the stashes
     dib_adam_step                                Keras Adam over ONE flat buffer holding all four networks
-There is no CPU fallback: a shape outside dib_measure_supported raises."""
+There is no CPU fallback: a shape outside dib_measure_supported raises.
+
+MeasurementEnsemble trains R such models of one architecture in lockstep (the notebook's 20 repeats per number_states): the same
+step with the replica as the group of every grouped GEMM and as a grid index of dib_measure_fwd_batched / _bwd_batched and
+dib_infonce_fwd_bwd_batched, so that the number of launches of a step does not depend on R."""
 from __future__ import annotations
 
 import ctypes
@@ -22,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib, ctw, utils
-from ._gemm_plan import _ptr
+from ._gemm_plan import _Gemm, _d, _ptr
 from ._lib import ACTIVATIONS, SIMILARITIES, check
 from .dense import DenseStack
 
@@ -359,3 +363,390 @@ def characterize_partition(symbolic_sequence, alphabet_size: int, number_data_po
     fit = entropy_rate_fit(seq, alphabet_size, number_data_points, number_rand_draws, seed, threads=int(threads or 0),
                            ctw_backend=ctw_backend)
     return {"entropy_single_timestep": h_u, **fit}
+
+
+# ---- R models in lockstep ---------------------------------------------------------------------------------------------------
+class _EnsembleStack:
+    """One of the four networks of every replica: a DenseStack's layer chain with the replica as the GROUP of each grouped
+    launch (include/dib_st.h dib_gemm_grouped: R descriptors per layer).  Row buffers are [R][n][width] contiguous - what the
+    batched measurement and InfoNCE kernels read and write; the weights of replica r sit at r * stride + base in the ensemble's
+    flat buffer, laid out as the template DenseStack lays them out."""
+
+    def __init__(self, owner, template: DenseStack, base: int):
+        self.o, self.t, self.base = owner, template, int(base)
+        self.dims, self.w_off, self.b_off, self.act, self.n_params = template.dims, template.w_off, template.b_off, template.act, \
+            template.n_params
+        self._plans: Dict[int, dict] = {}
+
+    def plan(self, n: int) -> dict:
+        pl = self._plans.get(n)
+        if pl is not None:
+            return pl
+        o, R, P, L = self.o, self.o.R, self.o.n_params, len(self.dims)
+        off, cur = {}, 0
+
+        def take(name, width):
+            nonlocal cur
+            off[name] = cur
+            cur = (cur + R * n * int(width) + 3) // 4 * 4
+
+        take("a0", self.dims[0][0])
+        for l, (_, wo) in enumerate(self.dims):
+            take(f"a{l + 1}", wo)                       # post-activation output of layer l, every replica
+            take(f"g{l + 1}", wo)                       # dL/d(pre-activation of layer l)
+        ws = torch.zeros(cur, dtype=torch.float32, device=o.device)
+        nsplit = max(1, min(32, n // 64))               # DenseStack's slab rule
+        rps = ((n + nsplit - 1) // nsplit + 31) // 32 * 32
+        nsplit = (n + rps - 1) // rps
+        pw = lambda r, l: r * P + self.base + self.w_off[l]
+        pb = lambda r, l: r * P + self.base + self.b_off[l]
+        g = {}
+        for l, (wi, wo) in enumerate(self.dims):
+            act = self.act if l < L - 1 else 0
+            g[f"fwd{l}"] = _Gemm(0, [_d(off[f"a{l}"] + r * n * wi, wi, pw(r, l), wo, off[f"a{l + 1}"] + r * n * wo, wo, n, wo, wi,
+                                        bias_off=pb(r, l)) for r in range(R)], ws, o.params, ws, bias=o.params, act=act)
+            if l > 0:
+                g[f"dgrad{l}"] = _Gemm(1, [_d(off[f"g{l + 1}"] + r * n * wo, wo, pw(r, l), wo, off[f"g{l}"] + r * n * wi, wi, n, wi, wo,
+                                              aux_off=off[f"a{l}"] + r * n * wi, ldaux=wi) for r in range(R)],
+                                       ws, o.params, ws, aux=ws, act=self.act)
+        for gg in g.values():
+            gg.upload(o.device)
+        if len(self._plans) >= 4:
+            self._plans.pop(next(iter(self._plans)))
+        pl = self._plans[n] = dict(n=n, ws=ws, off=off, g=g, nsplit=nsplit, rps=rps, wgrad={})
+        return pl
+
+    def wgrad(self, pl: dict, target: torch.Tensor, split_stride: int) -> _Gemm:
+        """every replica's and every layer's weight gradient of this network in ONE grouped launch, into `target` (the gradient
+        buffer itself, or the ensemble's slabs `split_stride` floats apart)"""
+        key = (target.data_ptr(), split_stride)
+        gg = pl["wgrad"].get(key)
+        if gg is None:
+            R, P, n, off = self.o.R, self.o.n_params, pl["n"], pl["off"]
+            gg = _Gemm(2, [_d(off[f"a{l}"] + r * n * wi, wi, off[f"g{l + 1}"] + r * n * wo, wo, r * P + self.base + self.w_off[l], wo,
+                              wi, wo, n, bias_off=r * P + self.base + self.b_off[l])
+                           for r in range(R) for l, (wi, wo) in enumerate(self.dims)], pl["ws"], pl["ws"], target, bias_out=target,
+                       nsplit=pl["nsplit"], rows_per_split=pl["rps"], split_stride=split_stride)
+            gg.upload(self.o.device)
+            pl["wgrad"] = {key: gg}
+        return gg
+
+    def view(self, pl, name, width):
+        o = pl["off"][name]
+        return pl["ws"][o: o + self.o.R * pl["n"] * width].view(self.o.R, pl["n"], width)
+
+    def forward(self, pl, st):
+        for l in range(len(self.dims)):
+            pl["g"][f"fwd{l}"].run(self.o.lib, st)
+
+    def dgrad(self, pl, st):
+        for l in reversed(range(1, len(self.dims))):
+            pl["g"][f"dgrad{l}"].run(self.o.lib, st)
+
+
+class MeasurementEnsemble:
+    """`replicas` MeasurementIB models of ONE architecture trained in lockstep - the notebook's "20 repeats per number_states":
+    they differ in their initial weights, their noise seeds and the batches they draw, and share every launch of a step.
+
+    Replica r starts from the weights of MeasurementIB(init_seed=init_seeds[r], noise_seed=noise_seeds[r], ...) (defaults:
+    init_seed + 4 r - a model seeds its four networks init_seed .. init_seed + 3 - and noise_seed + r).  One flat buffer
+    params | grads | m | v, replica-major, each replica laid out like MeasurementIB's; one dib_adam_step per step with a shared
+    learning rate, step count and beta.  Per step: one gather + positional encoding of all R B L rows, every Dense layer as one
+    grouped launch of R descriptors, dib_measure_fwd_batched / _bwd_batched, dib_infonce_fwd_bwd_batched (l1 / linf: the single
+    entry point per replica) - for the dot-product similarities the number of launches does not depend on R."""
+
+    def __init__(self, replicas: int, init_seeds: Optional[Sequence[int]] = None, noise_seeds: Optional[Sequence[int]] = None,
+                 **kwargs):
+        R = int(replicas)
+        if R < 1:
+            raise ValueError("replicas >= 1")
+        init_seed, noise_seed = int(kwargs.pop("init_seed", 0)), int(kwargs.pop("noise_seed", 0))
+        self.init_seeds = [int(s) for s in init_seeds] if init_seeds is not None else [init_seed + 4 * r for r in range(R)]
+        self.noise_seeds = [int(s) for s in noise_seeds] if noise_seeds is not None else [noise_seed + r for r in range(R)]
+        if len(self.init_seeds) != R or len(self.noise_seeds) != R:
+            raise ValueError(f"init_seeds and noise_seeds take one seed per replica ({R})")
+        self.R, self._kwargs = R, dict(kwargs)
+        # replica 0 as a MeasurementIB: validates the arguments (before any launch), fixes the layout, and is the template
+        m0 = self._template = MeasurementIB(init_seed=self.init_seeds[0], noise_seed=self.noise_seeds[0], **kwargs)
+        for k in ("d", "L", "A", "E", "p", "n_freq", "reference_timestep", "D", "similarity", "temperature", "eng", "lib", "device",
+                  "_desc", "n_params"):
+            setattr(self, k, getattr(m0, k))
+        P = self.n_params
+        flat = torch.zeros(4 * R * P, dtype=torch.float32, device=self.device)
+        self.params, self.grads, self.adam_m, self.adam_v = (flat[i * R * P: (i + 1) * R * P] for i in range(4))
+        self._flat = flat
+        bases = [int((s.params.data_ptr() - m0.params.data_ptr()) // 4) for s in m0._stacks]
+        self.params[:P].copy_(m0.params)
+        act = kwargs.get("activation_function", "leaky_relu")
+        for r in range(1, R):   # the other replicas' initial weights: the DenseStack initialiser with their seeds
+            for k, (s, b) in enumerate(zip(m0._stacks, bases)):
+                init = DenseStack(self.eng, s.input_dim, [o for _, o in s.dims[:-1]], s.dims[-1][1], act, s.n_freq > 1, s.n_freq,
+                                  seed=self.init_seeds[r] + k)
+                assert init.n_params == s.n_params
+                self.params[r * P + b: r * P + b + s.n_params].copy_(init.params)
+        self.ib, self.vq, self.agg, self.ref = (_EnsembleStack(self, s, b) for s, b in zip(m0._stacks, bases))
+        self._nets = {"ib": self.ib, "vq": self.vq, "agg": self.agg, "ref": self.ref}
+        self._seeds_c = (ctypes.c_uint64 * R)(*[s & (2 ** 64 - 1) for s in self.noise_seeds])
+        self.t_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.lr_dev = torch.full((1,), 3e-4, dtype=torch.float32, device=self.device)
+        self.step, self.beta = 0, 10.0
+        self.snapshots: Dict[int, torch.Tensor] = {}    # parameters of retired replicas (fit)
+        self._bufs: Dict[int, dict] = {}
+        self._sym_ib: Optional[DenseStack] = None
+
+    # ---- one step ----------------------------------------------------------------------------
+    def _buffers(self, B: int) -> dict:
+        bf = self._bufs.get(B)
+        if bf is None:
+            R, lib, f = self.R, self.lib, lambda *s: torch.zeros(*s, dtype=torch.float32, device=self.device)
+            pls = dict(ib=self.ib.plan(B * self.L), vq=self.vq.plan(B * self.L), agg=self.agg.plan(B), ref=self.ref.plan(B))
+            nmax = max(pl["nsplit"] for pl in pls.values())
+            bf = dict(pl=pls, out3=f(R, 3), lp=f(R), gx=f(R, B, self.D), gy=f(R, B, self.D), nsplit=nmax,
+                      slabs=f(nmax * R * self.n_params) if nmax > 1 else None,
+                      ws=torch.zeros(int(lib.dib_measure_batched_workspace_bytes(ctypes.byref(self._desc), B * self.L, R)) // 4 + 1,
+                                     dtype=torch.float32, device=self.device),
+                      # (l1 / linf: the single entry point's workspace, used by one replica after the other)
+                      nce_ws=torch.empty(int(lib.dib_infonce_batched_workspace_bytes(R, B) if self.similarity in (0, 1, 4)
+                                             else lib.dib_infonce_workspace_bytes(B)) // 4 + 1, dtype=torch.float32,
+                                         device=self.device),
+                      offs=torch.arange(self.L, dtype=torch.int32, device=self.device))
+            # networks whose own rule gives one slab accumulate into slab 0 next to the others': it is cleared every step
+            bf["clear_slab0"] = nmax > 1 and any(pl["nsplit"] == 1 for pl in pls.values())
+            if len(self._bufs) >= 2:
+                self._bufs.pop(next(iter(self._bufs)))
+            self._bufs[B] = bf
+        return bf
+
+    def _step(self, traj: torch.Tensor, starts: torch.Tensor, beta: float, training: bool) -> dict:
+        lib, st, R, P = self.lib, self.eng._stream(), self.R, self.n_params
+        B, L, A, E, d = int(starts.shape[1]), self.L, self.A, self.E, self._desc
+        n = B * L
+        bf = self._buffers(B)
+        ib, vq, agg, ref = (bf["pl"][k] for k in ("ib", "vq", "agg", "ref"))
+        rows = (starts.view(R, B, 1) + bf["offs"].view(1, 1, L)).reshape(-1)
+        check(lib.dib_positional_encoding_rows(_ptr(traj), traj.stride(0), _ptr(rows), R * n, self.d, self.n_freq,
+                                               _ptr(ib["ws"], ib["off"]["a0"]), st), "dib_positional_encoding_rows")
+        self.ib.forward(ib, st)
+        enc = self.ib.view(ib, f"a{len(self.ib.dims)}", 2 * E)                   # [R, n, 2E] = mu | logvar
+        vw = lambda name: _ptr(vq["ws"], vq["off"][name])
+        soft = _ptr(agg["ws"], agg["off"]["a0"])                                 # [R][n][A] = the aggregator's input [R][B][L A]
+        vqp = _ptr(self.params, self.vq.base)
+        check(lib.dib_measure_fwd_batched(ctypes.byref(d), vqp, P, _ptr(enc), n, R, self._seeds_c, self.step & 0xFFFFFFFF, float(beta),
+                                          self.p, vw("a0"), vw("a1"), vw("a2"), soft, _ptr(bf["out3"]), _ptr(bf["ws"]), st),
+              "dib_measure_fwd_batched")
+        self.agg.forward(agg, st)
+        ref_rows = (starts + self.reference_timestep).reshape(-1)
+        check(lib.dib_measure_posenc_rows(_ptr(traj), traj.stride(0), _ptr(ref_rows), R * B, self.d, self.n_freq, 0,
+                                          _ptr(ref["ws"], ref["off"]["a0"]), st), "dib_measure_posenc_rows")
+        self.ref.forward(ref, st)
+        seq = self.agg.view(agg, f"a{len(self.agg.dims)}", self.D)
+        remb = self.ref.view(ref, f"a{len(self.ref.dims)}", self.D)
+        gx, gy = (bf["gx"], bf["gy"]) if training else (None, None)
+        if self.similarity in (0, 1, 4):
+            check(lib.dib_infonce_fwd_bwd_batched(_ptr(seq), _ptr(remb), R, B, self.D, self.similarity, self.temperature, _ptr(gx),
+                                                  _ptr(gy), _ptr(bf["lp"]), _ptr(bf["nce_ws"]), st), "dib_infonce_fwd_bwd_batched")
+        else:   # l1 / linf: no batched kernel - the single entry point, replica by replica
+            for r in range(R):
+                check(lib.dib_infonce_fwd_bwd(_ptr(seq[r]), _ptr(remb[r]), B, self.D, self.similarity, self.temperature,
+                                              _ptr(gx[r]) if training else None, _ptr(gy[r]) if training else None,
+                                              _ptr(bf["lp"][r:]), _ptr(bf["nce_ws"]), st), "dib_infonce_fwd_bwd")
+        if training:
+            slabs, stride = bf["slabs"], R * P
+            target = slabs if slabs is not None else self.grads
+            if slabs is None:
+                self.grads.zero_()
+            elif bf["clear_slab0"]:
+                slabs[:stride].zero_()
+            # the library's InfoNCE is the sum of both directions; the notebook halves it
+            torch.mul(gx, 0.5, out=self.agg.view(agg, f"g{len(self.agg.dims)}", self.D))
+            self.agg.dgrad(agg, st)
+            self.agg.wgrad(agg, target, stride).run(lib, st)
+            torch.mul(gy, 0.5, out=self.ref.view(ref, f"g{len(self.ref.dims)}", self.D))
+            self.ref.dgrad(ref, st)
+            self.ref.wgrad(ref, target, stride).run(lib, st)
+            HA = self.agg.dims[0][1]
+            check(lib.dib_measure_bwd_batched(ctypes.byref(d), vqp, P, _ptr(enc), n, R, self._seeds_c, self.step & 0xFFFFFFFF,
+                                              vw("a1"), vw("a2"), soft, _ptr(agg["ws"], agg["off"]["g1"]),
+                                              _ptr(self.params, self.agg.base + self.agg.w_off[0]), P, HA, _ptr(bf["out3"]),
+                                              vw("g3"), vw("g2"), vw("g1"), _ptr(ib["ws"], ib["off"][f"g{len(self.ib.dims)}"]), st),
+                  "dib_measure_bwd_batched")
+            self.vq.wgrad(vq, target, stride).run(lib, st)
+            self.ib.dgrad(ib, st)
+            self.ib.wgrad(ib, target, stride).run(lib, st)
+            if slabs is not None:
+                check(lib.dib_reduce_splits(_ptr(slabs), stride, bf["nsplit"], stride, _ptr(self.grads), st), "dib_reduce_splits")
+            check(lib.dib_adam_step(_ptr(self.params), _ptr(self.grads), _ptr(self.adam_m), _ptr(self.adam_v), stride,
+                                    _ptr(self.lr_dev), _ptr(self.t_dev), 0.9, 0.999, 1e-7, 1.0, st), "dib_adam_step")
+            self.step += 1
+        return bf
+
+    def match_batch_from_starts(self, traj_dev: torch.Tensor, starts, training: bool = True, beta: Optional[float] = None):
+        """One step of every replica on its own sequences traj[starts[r, b] .. + L): starts [R, B].  Returns fresh device
+        vectors [R] (loss, loss_prediction, kl) without synchronising."""
+        starts = torch.as_tensor(starts).to(device=self.device, dtype=torch.int32)
+        if starts.dim() != 2 or starts.shape[0] != self.R:
+            raise ValueError(f"starts must be [replicas = {self.R}, batch]")
+        bf = self._step(traj_dev, starts.contiguous(), self.beta if beta is None else beta, training)
+        kl, lkl, lp = bf["out3"][:, 0].clone(), bf["out3"][:, 1], bf["lp"] * 0.5
+        return lkl + lp, lp, kl
+
+    def match_batch(self, states_batch, training: bool = True, beta: Optional[float] = None):
+        """host batches [R, B, L, d], one per replica: (loss, loss_prediction, kl) as NumPy vectors [R]"""
+        x = np.ascontiguousarray(np.asarray(states_batch, dtype=np.float32))
+        R, B, L, d = x.shape
+        assert R == self.R and L == self.L and d == self.d
+        traj = torch.from_numpy(x.reshape(R * B * L, d)).to(self.device)
+        starts = torch.arange(0, R * B * L, L, dtype=torch.int32, device=self.device).view(R, B)
+        return tuple(v.cpu().numpy() for v in self.match_batch_from_starts(traj, starts, training, beta))
+
+    # ---- training loop -----------------------------------------------------------------------
+    def _info_bounds(self, x: np.ndarray, bs: int, nb: int, seed: int) -> np.ndarray:
+        """[R, 2] sandwich bounds of I(U~; X) in nats at the current weights: the batches utils.estimate_mi_sandwich_bounds draws
+        for `seed` (the same rows for every replica), ONE grouped forward of every replica's IB encoder on them, and one
+        dib_mi_sandwich_batched over the R nb batches (batch b of replica r keyed (seed, r nb + b, position, 0)); where that
+        kernel does not take the shape (E not a multiple of 4), dib_mi_sandwich_rows batch by batch."""
+        lib, st, R, E = self.lib, self.eng._stream(), self.R, self.E
+        rng, n = np.random.default_rng(seed), x.shape[0]
+        rows = np.concatenate([rng.permutation(n)[:bs] if n >= bs else rng.integers(0, n, bs) for _ in range(nb)])
+        xb = torch.from_numpy(x[rows]).to(self.device)
+        m = nb * bs
+        pl = self.ib.plan(m)
+        idx = torch.arange(m, dtype=torch.int32, device=self.device).repeat(R)
+        check(lib.dib_positional_encoding_rows(_ptr(xb), xb.stride(0), _ptr(idx), R * m, self.d, self.n_freq,
+                                               _ptr(pl["ws"], pl["off"]["a0"]), st), "dib_positional_encoding_rows")
+        self.ib.forward(pl, st)
+        enc = self.ib.view(pl, f"a{len(self.ib.dims)}", 2 * E)
+        need = int(lib.dib_mi_sandwich_batched_workspace_bytes(R * m, 1, E, R * nb, bs))
+        if need < 0:
+            out = [[utils.mi_sandwich_rows(lib, self.device, enc[r, b * bs: (b + 1) * bs], seed, b, 0).mean(dim=1).cpu().numpy()
+                    for b in range(nb)] for r in range(R)]
+            return np.mean(np.asarray(out), 1)
+        ws = torch.empty(need // 8 + 2, dtype=torch.float64, device=self.device)
+        out = torch.empty((2, R * nb), dtype=torch.float64, device=self.device)
+        bidx = torch.arange(R * m, dtype=torch.int32, device=self.device)
+        check(lib.dib_mi_sandwich_batched(_ptr(enc), R * m, 1, E, _ptr(bidx), R * nb, bs, 0.0, int(seed) & (2 ** 64 - 1), 0,
+                                          _ptr(out[0]), _ptr(out[1]), None, None, None, _ptr(ws), st), "dib_mi_sandwich_batched")
+        return out.view(2, R, nb).mean(dim=2).cpu().numpy().T.copy()
+
+    def fit(self, train_trajectory, number_training_steps: int = 20_000, batch_size: int = 2048, learning_rate: float = 3e-4,
+            beta_start: float = 10., beta_end: float = 1e-4, info_eval_data=None, evaluate_info_every: Optional[int] = None,
+            info_evaluation_batch_size: int = 1024, info_evaluation_number_batches: int = 8, info_stopping_point=1.0,
+            seeds: Optional[Sequence[int]] = None) -> List[dict]:
+        """MeasurementIB.fit for every replica at once.  Replica r draws its start indices from np.random.default_rng(seeds[r])
+        (default r) - the stream a single fit(seed=seeds[r]) draws; one [R, B] upload per step.  Every `evaluate_info_every`
+        steps the sandwich bounds of every replica are evaluated; a replica whose mean bound reaches its `info_stopping_point`
+        (a scalar, or one per replica) is RETIRED: its parameters are copied to `snapshots[r]` and its history ends there,
+        while the lockstep step goes on computing it so that nothing the others see changes.  Ends when every replica is
+        retired or the steps run out.  Returns one history per replica with the keys of MeasurementIB.fit."""
+        R = self.R
+        traj = torch.as_tensor(np.ascontiguousarray(np.asarray(train_trajectory, dtype=np.float32))).to(self.device)
+        if traj.dim() == 1:
+            traj = traj[:, None].contiguous()
+        n_starts = traj.shape[0] - self.L
+        seeds = list(range(R)) if seeds is None else [int(s) for s in seeds]
+        thr = np.broadcast_to(np.asarray(info_stopping_point, dtype=np.float64), (R,)) if np.ndim(info_stopping_point) == 0 \
+            else np.asarray(info_stopping_point, dtype=np.float64)
+        if len(seeds) != R or thr.shape != (R,):
+            raise ValueError(f"seeds and info_stopping_point take one entry per replica ({R})")
+        rngs = [np.random.default_rng(s) for s in seeds]
+        self.lr_dev.fill_(float(learning_rate))
+        every = evaluate_info_every if evaluate_info_every is not None else max(1, number_training_steps // 100)
+        ev = None
+        if info_eval_data is not None:
+            ev = np.asarray(info_eval_data, dtype=np.float32)
+            ev = ev[:, None] if ev.ndim == 1 else ev
+        hist = torch.zeros((number_training_steps, 2, R), dtype=torch.float32, device=self.device)
+        out = [{"loss": [], "info_in": [], "info_out": [], "beta": []} for _ in range(R)]
+        done = [None] * R                                    # steps taken when the replica retired
+        betas, taken = [], 0
+        self.snapshots = {}
+        for step_num in range(number_training_steps):
+            self.beta = beta = beta_schedule(step_num, number_training_steps, beta_start, beta_end)
+            betas.append(beta)
+            starts = np.stack([g.choice(n_starts, size=batch_size) for g in rngs]).astype(np.int32)
+            loss, lp, _ = self.match_batch_from_starts(traj, torch.from_numpy(starts).to(self.device, non_blocking=True), True)
+            hist[step_num, 0].copy_(loss)
+            hist[step_num, 1].copy_(lp)
+            taken = step_num + 1
+            if ev is not None and taken % every == 0:
+                info = np.float32(self._info_bounds(ev, int(info_evaluation_batch_size), int(info_evaluation_number_batches),
+                                                    step_num)) / np.log(2)
+                lpv = hist[step_num, 1].cpu().numpy()
+                for r in range(R):
+                    if done[r] is not None:
+                        continue
+                    out[r]["info_in"].append(info[r])
+                    out[r]["info_out"].append((np.log2(batch_size) - float(lpv[r]) / np.log(2)) / self.L)
+                    if np.mean(info[r]) >= thr[r]:
+                        done[r] = taken
+                        self.snapshots[r] = self.params[r * self.n_params: (r + 1) * self.n_params].clone()
+                if all(s is not None for s in done):
+                    break
+        losses = hist[:taken, 0].cpu().numpy()
+        for r in range(R):
+            k = taken if done[r] is None else done[r]
+            out[r]["loss"] = losses[:k, r].tolist()
+            out[r]["beta"] = betas[:k]
+            out[r]["steps"] = k
+        return out
+
+    # ---- access to replicas ------------------------------------------------------------------
+    def _replica_params(self, r: int) -> torch.Tensor:
+        """replica r's parameters [n_params]: its snapshot if fit retired it, else its slice of the live buffer"""
+        if not 0 <= int(r) < self.R:
+            raise IndexError(f"replica {r} of {self.R}")
+        snap = self.snapshots.get(int(r))
+        return snap if snap is not None else self.params[r * self.n_params: (r + 1) * self.n_params]
+
+    def get_weights(self, r: int) -> Dict[str, List[np.ndarray]]:
+        """{"ib", "vq", "agg", "ref"} -> Keras-ordered [kernel, bias] per layer (of the snapshot if replica r is retired)"""
+        p = self._replica_params(r).cpu().numpy()
+        return {k: sum(([p[s.base + w: s.base + w + i * o].reshape(i, o).copy(), p[s.base + b: s.base + b + o].copy()]
+                        for (i, o), w, b in zip(s.dims, s.w_off, s.b_off)), []) for k, s in self._nets.items()}
+
+    def set_weights(self, r: int, weights: Dict[str, Sequence[np.ndarray]]) -> None:
+        """the live parameters of replica r (a snapshot fit left for it is dropped)"""
+        self._replica_params(r)
+        live = self.params[r * self.n_params: (r + 1) * self.n_params]
+        for k, ws in weights.items():
+            s = self._nets[k]
+            assert len(ws) == 2 * len(s.dims)
+            for l, ((i, o), w, b) in enumerate(zip(s.dims, s.w_off, s.b_off)):
+                live[s.base + w: s.base + w + i * o].copy_(torch.as_tensor(np.asarray(ws[2 * l], dtype=np.float32).reshape(-1)))
+                live[s.base + b: s.base + b + o].copy_(torch.as_tensor(np.asarray(ws[2 * l + 1], dtype=np.float32).reshape(-1)))
+        self.snapshots.pop(int(r), None)
+
+    def to_model(self, r: int) -> MeasurementIB:
+        """a MeasurementIB carrying replica r's weights (the snapshot if retired), noise seed and step: symbolize,
+        characterize_partition and the CTW back ends apply to it unchanged"""
+        p = self._replica_params(r)
+        m = MeasurementIB(init_seed=self.init_seeds[r], noise_seed=self.noise_seeds[r], **self._kwargs)
+        m.params.copy_(p)
+        m.step, m.beta = self.step, self.beta
+        return m
+
+    def symbolize(self, r: int, data, number_averaging_logits: int = 100, noise_vector=None, seed: int = 0,
+                  chunk_size: int = 1 << 18, return_counts: bool = False):
+        """MeasurementIB.symbolize for replica r: its IB encoder on a DenseStack, dib_measure_symbolize on ITS packed VQ
+        parameters where they lie in the ensemble's buffer (in its snapshot if retired)"""
+        p = self._replica_params(r)
+        x = torch.as_tensor(np.ascontiguousarray(np.asarray(data, dtype=np.float32))).to(self.device)
+        if x.dim() == 1:
+            x = x[:, None].contiguous()
+        if noise_vector is None:
+            noise_vector = np.random.default_rng(seed).standard_normal((int(number_averaging_logits), self.E))
+        noise = torch.as_tensor(np.asarray(noise_vector, dtype=np.float32).reshape(-1, self.E)).to(self.device).contiguous()
+        K, n = int(noise.shape[0]), int(x.shape[0])
+        sym = torch.empty(n, dtype=torch.uint8, device=self.device)
+        counts = torch.empty((n, self.A), dtype=torch.int32, device=self.device) if return_counts else None
+        enc_stack = self._template.ib                         # the template's encoder stack, loaded with replica r's weights
+        enc_stack.params.copy_(p[self.ib.base: self.ib.base + self.ib.n_params])
+        st = self.eng._stream()
+        for c0 in range(0, n, int(chunk_size)):
+            c1 = min(n, c0 + int(chunk_size))
+            enc = enc_stack.forward(x[c0:c1])
+            check(self.lib.dib_measure_symbolize(ctypes.byref(self._desc), _ptr(p, self.vq.base), _ptr(enc), c1 - c0, _ptr(noise), K,
+                                                 _ptr(sym[c0:c1]), _ptr(counts[c0:c1]) if counts is not None else None, st),
+                  "dib_measure_symbolize")
+        s = sym.cpu().numpy()
+        return (s, counts.cpu().numpy()) if return_counts else s

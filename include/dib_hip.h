@@ -345,6 +345,14 @@ int dib_bhattacharyya(const float* mu1, const float* lv1, int n, const float* mu
 int64_t dib_infonce_workspace_bytes(int batch);
 int dib_infonce_fwd_bwd(const float* emb_x, const float* emb_y, int batch, int dim, int similarity, float temperature,
                         float* g_x, float* g_y, float* loss_out, void* ws, dib_stream_t stream);
+/* `replicas` independent problems emb_x, emb_y, g_x, g_y [replicas][batch][dim], loss_out [replicas], in as many launches as
+ * ONE problem takes: the replica is a grid index, every replica has its own slice of the workspace and its own arrival counter,
+ * and replica r's loss and gradients are, bit for bit, dib_infonce_fwd_bwd's on its slices.  g_x / g_y NULL: the losses only.
+ * The dot-product similarities (0 'l2sq', 1 'l2', 4 'cosine') on both of their routes; 2 'l1' and 3 'linf' return
+ * DIB_E_UNSUPPORTED with nothing launched (call dib_infonce_fwd_bwd per replica). */
+int64_t dib_infonce_batched_workspace_bytes(int replicas, int batch);
+int dib_infonce_fwd_bwd_batched(const float* emb_x, const float* emb_y, int replicas, int batch, int dim, int similarity,
+                                float temperature, float* g_x, float* g_y, float* loss_out, void* ws, dib_stream_t stream);
 /* PositionalEncoding.call (models.py:22-23) of one dense [n, d] matrix -> [n, d*n_freq] (train.py:186-188: Y encoder) */
 int dib_positional_encoding(const float* x, int64_t ldx, int n, int d, int n_freq, float* out, dib_stream_t stream);
 /* the same of rows row_idx[0..n) of x (the shuffled batch of the custom loop, train.py:226-227); n_freq <= 1: a plain gather */

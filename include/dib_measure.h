@@ -39,6 +39,22 @@ int dib_measure_fwd(const dib_measure_desc* d, const float* params, const float*
 int dib_measure_bwd(const dib_measure_desc* d, const float* params, const float* enc, int rows, uint64_t seed, uint32_t step,
                     const float* h1, const float* h2, const float* soft, const float* g_agg, const float* w_agg0,
                     int agg_width, const float* out3, float* g3, float* g2, float* g1, float* g_enc, dib_stream_t stream);
+/* ---- `replicas` independent models of one shape in one launch each (MeasurementEnsemble) ----
+ * Replica r has its packed VQ parameters at params + r * param_stride (a multiple of 4 floats), its noise seed seeds[r] (a HOST
+ * array, read before the call returns) and slice r of every row buffer: enc, z, h1, h2, soft, g3, g2, g1, g_enc are
+ * [replicas][rows][...] contiguous, g_agg [replicas][rows / L][agg_width], w_agg0 at w_agg0 + r * w_agg0_stride, out3
+ * [replicas][3].  The row index of the noise key is local to the replica (row = b * L + l), so replica r computes, bit for bit,
+ * what dib_measure_fwd / dib_measure_bwd compute on its slices with seed seeds[r]: the replica is an outer grid index, each
+ * replica sums its own KL partials behind its own arrival counter, and no workgroup waits on another.  One launch each for up
+ * to 64 replicas (one more per further 64).  Workspace of the forward: dib_measure_batched_workspace_bytes, zero-filled once. */
+int64_t dib_measure_batched_workspace_bytes(const dib_measure_desc* d, int rows, int replicas);
+int dib_measure_fwd_batched(const dib_measure_desc* d, const float* params, int64_t param_stride, const float* enc, int rows,
+                            int replicas, const uint64_t* seeds, uint32_t step, float beta, float kl_exponent, float* z, float* h1,
+                            float* h2, float* soft, float* out3, void* ws, dib_stream_t stream);
+int dib_measure_bwd_batched(const dib_measure_desc* d, const float* params, int64_t param_stride, const float* enc, int rows,
+                            int replicas, const uint64_t* seeds, uint32_t step, const float* h1, const float* h2,
+                            const float* soft, const float* g_agg, const float* w_agg0, int64_t w_agg0_stride, int agg_width,
+                            const float* out3, float* g3, float* g2, float* g1, float* g_enc, dib_stream_t stream);
 /* Symbolisation of n points from their encodings enc [n][2E]: for each of the K noise vectors noise [K][E],
  * argmax(VQ(mu + noise_k * exp(logvar / 2))) (first maximum wins); sym[i] = (mean_k argmax > 0.5) as uint8 - the reference's
  * rule for every alphabet size; counts [n][A] (may be NULL): how often each symbol was the argmax. */

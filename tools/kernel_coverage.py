@@ -53,6 +53,11 @@ ORACLE_TESTS = {
     "test_gpu_measurement.py": {
         "test_step_losses_and_all_gradients_match_oracle", "test_train_steps_through_the_beta_ramp_match_oracle_adam",
         "test_symbolize_matches_oracle", "test_mi_sandwich_bounds_of_the_ib_encoder_match_oracle"},
+    "test_gpu_measurement_batched_kernels.py": {
+        "test_measure_batched_equals_the_single_kernels_and_the_oracle",
+        "test_infonce_batched_equals_the_single_entry_point_and_the_oracle", "test_infonce_batched_wide_embeddings"},
+    "test_gpu_measurement_ensemble.py": {
+        "test_step_losses_and_all_gradients_of_every_replica_match_oracle", "test_train_steps_through_the_beta_ramp_match_oracle_adam"},
     "test_gpu_circuit.py": {
         "test_drawn_rows_eps_and_u_match_oracle", "test_step_bce_kl_and_all_gradients_match_oracle",
         "test_thirty_adam_steps_through_the_beta_ramp_match_oracle", "test_mi_bounds_match_compute_batch_and_the_per_gate_loop"},
@@ -163,6 +168,9 @@ EQUIVALENCE_TESTS = {
         "test_placement_does_not_change_the_bits", "test_graph_replay_has_the_eager_bits",
         "test_fit_on_a_device_tensor_equals_fit_on_numpy_bit_for_bit"},
     "test_gpu_subset_information.py": {"test_chunks_and_placement_do_not_change_the_bits", "test_graph_replay_has_the_eager_bits"},
+    "test_gpu_measurement_ensemble.py": {
+        "test_a_replica_does_not_see_the_others", "test_fit_retires_replicas_at_their_own_thresholds",
+        "test_one_replica_as_a_model_and_its_symbols"},
     "test_gpu_ctw_levels.py": {
         "test_chunks_do_not_change_the_bits_and_an_overflowing_window_goes_to_the_host",
         "test_entropy_rate_fit_on_the_device_backend", "test_random_partition_characterize_keeps_the_symbols_on_the_device"},
