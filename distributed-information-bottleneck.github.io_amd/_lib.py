@@ -160,6 +160,11 @@ SIGNATURES = {
     "dib_philox_normal_fill": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_uint64, c_uint32,
                                        c_void_p]),
     "dib_philox_normal_ref": (c_float, [c_uint64, c_uint32, c_uint32, c_uint32, c_uint32]),
+    "dib_mlp_small_head_batched_supported": (c_int, [c_void_p, c_int, c_int]),
+    "dib_mlp_small_head_batched_workspace_bytes": (c_int64, [c_void_p, c_int, c_int]),
+    "dib_mlp_small_head_step_batched": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_float,
+                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                                c_void_p, c_void_p]),
     "dib_launch_count": (c_int64, []),
     "dib_profile_enable": (c_int, [c_int]),
     "dib_profile_summary": (c_int, [POINTER(ctypes.c_double), POINTER(c_int)]),
@@ -253,6 +258,14 @@ SIGNATURES_CIRCUIT = {
                                 c_void_p]),
     "dib_circuit_mi_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "dib_circuit_mi_bounds": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_uint64, c_void_p, c_void_p, c_void_p]),
+    "dib_circuit_batched_supported": (c_int, [c_void_p, c_int, c_int]),
+    "dib_circuit_fwd_batched": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_void_p,
+                                        c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dib_circuit_bwd_batched": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_void_p,
+                                        c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "dib_circuit_mi_batched_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "dib_circuit_mi_bounds_batched": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                              c_void_p, c_void_p]),
 }
 
 # include/dib_partition.h: the chaos notebook's random-MLP partitions

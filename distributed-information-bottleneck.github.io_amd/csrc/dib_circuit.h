@@ -38,33 +38,9 @@ __global__ void __launch_bounds__(256)
 dib_circuit_fwd_kernel(const uint32_t* __restrict__ table, int G, int B, const float* __restrict__ sc, uint64_t seed, uint32_t step,
                        float beta, const int32_t* __restrict__ row_in, int32_t* __restrict__ row_out, float* __restrict__ u,
                        float* __restrict__ y, float* __restrict__ kl) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  const int b = idx >> 4, k = idx & 15;
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    float tot = 0.f;
-    for (int g = 0; g < G; ++g) {
-      const float s = sc[g], lv = sc[G + g];
-      const float v = 0.5f * (s * s + expf(lv) - lv - 1.f);
-      kl[g] = v;
-      tot += v;
-    }
-    kl[G] = beta * tot;
-  }
-  if (b >= B) return;
-  const uint32_t mask = (1u << G) - 1u;
-  // a caller's index is taken modulo 2^G: no read outside the table whatever it holds
-  const uint32_t r = row_in ? ((uint32_t)row_in[b] & mask) : dib_circuit_draw_row(seed, step, (uint32_t)b, G);
-  const uint32_t bits = table[r];
-  float v = 0.f;
-  if (k < G) {
-    const float x = ((bits >> k) & 1u) ? 1.f : -1.f;
-    v = x * sc[k] + expf(0.5f * sc[G + k]) * dib_circuit_eps(seed, step, (uint32_t)b, (uint32_t)k);
-  }
-  u[(long long)b * DIB_CIRCUIT_LD + k] = v;
-  if (k == 0) {
-    row_out[b] = (int32_t)r;
-    y[b] = (float)((bits >> G) & 1u);
-  }
+#define DIB_CIRCUIT_BODY 1
+#include "dib_circuit_bodies.h"
+#undef DIB_CIRCUIT_BODY
 }
 
 // one workgroup per gate: ds_g = sum_b g_u[b][g] x[b][g] + beta s_g, dlv_g = sum_b g_u[b][g] eps[b][g] exp(lv_g / 2) / 2 +
@@ -72,31 +48,10 @@ dib_circuit_fwd_kernel(const uint32_t* __restrict__ table, int G, int B, const f
 __global__ void __launch_bounds__(256)
 dib_circuit_bwd_kernel(const uint32_t* __restrict__ table, int G, int B, const float* __restrict__ sc, uint64_t seed, uint32_t step,
                        float beta, const int32_t* __restrict__ rows, const float* __restrict__ g_u, float* __restrict__ g_sc) {
-  __shared__ double rs[256], rl[256];
   const int g = blockIdx.x;
-  double as = 0.0, al = 0.0;
-  for (int b = threadIdx.x; b < B; b += 256) {
-    const uint32_t bits = table[(uint32_t)rows[b] & ((1u << G) - 1u)];
-    const double x = ((bits >> g) & 1u) ? 1.0 : -1.0;
-    const double gu = (double)g_u[(long long)b * DIB_CIRCUIT_LD + g];
-    as += gu * x;
-    al += gu * (double)dib_circuit_eps(seed, step, (uint32_t)b, (uint32_t)g);
-  }
-  rs[threadIdx.x] = as;
-  rl[threadIdx.x] = al;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      rs[threadIdx.x] += rs[threadIdx.x + s];
-      rl[threadIdx.x] += rl[threadIdx.x + s];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    const double s = (double)sc[g], lv = (double)sc[G + g];
-    g_sc[g] = (float)(rs[0] + (double)beta * s);
-    g_sc[G + g] = (float)(rl[0] * 0.5 * exp(0.5 * lv) + (double)beta * 0.5 * (exp(lv) - 1.0));
-  }
+#define DIB_CIRCUIT_BODY 2
+#include "dib_circuit_bodies.h"
+#undef DIB_CIRCUIT_BODY
 }
 
 // Sandwich bounds of every gate's channel for nb evaluation batches of n points (x [nb][n] = +-1), eps of point i of batch b
@@ -111,66 +66,95 @@ dib_circuit_bwd_kernel(const uint32_t* __restrict__ table, int G, int B, const f
 __global__ void __launch_bounds__(256)
 dib_circuit_mi_kernel(const float* __restrict__ sc, int G, const float* __restrict__ xs, int n, int nb, uint64_t seed,
                       double* __restrict__ part_ws, unsigned* __restrict__ counters, double* __restrict__ out) {
-  __shared__ double rlo[DIB_CIRCUIT_MI_ROWS], rup[DIB_CIRCUIT_MI_ROWS];
-  __shared__ int last;
-  const int b = blockIdx.y, g = blockIdx.z, chunks = gridDim.x;
-  const int r = threadIdx.x >> 2, q = threadIdx.x & 3;
-  const int i = blockIdx.x * DIB_CIRCUIT_MI_ROWS + r;
-  const bool valid = i < n;
-  const float* x = xs + (long long)b * n;
-  const float s = sc[g];
-  const double l = (double)sc[G + g];
-  const double sd = exp(0.5 * l);
-  const double is = 1.0 / sd;
-  const double c = -0.5 * l - 0.5 * DIB_LN2PI;   // log N(0; 0, sigma^2)
-  const float mu_i = valid ? x[i] * s : 0.f;
-  const double ui = valid ? (double)mu_i + sd * (double)dib_circuit_eps(seed, (uint32_t)b, (uint32_t)i, (uint32_t)g) : 0.0;
-  double mx = -1.0e300, sm = 0.0;   // log-sum-exp over j != i
-  if (valid) {
-    for (int j = q; j < n; j += 4) {
-      if (j == i) continue;
-      const double d = (ui - (double)(x[j] * s)) * is;
-      dib_lse_add(mx, sm, c - 0.5 * (d * d));
-    }
-  }
-#pragma unroll
-  for (int o = 1; o <= 2; o <<= 1) {
-    const double m2 = __shfl_xor(mx, o, 64), s2 = __shfl_xor(sm, o, 64);
-    dib_lse_merge(mx, sm, m2, s2);
-  }
-  if (q == 0) {
-    double lo = 0.0, up = 0.0;
-    if (valid) {
-      const double d = (ui - (double)mu_i) * is;
-      const double lii = c - 0.5 * (d * d);
-      const double logn = log((double)n);
-      dib_sandwich_pair(lii, dib_lse_value(mx, sm), logn, logn, lo, up);
-    }
-    rlo[r] = lo;
-    rup[r] = up;
-  }
-  __syncthreads();
-  const long long pair = (long long)g * nb + b;
-  if (threadIdx.x == 0) {
-    double lo = 0.0, up = 0.0;
-    for (int k = 0; k < DIB_CIRCUIT_MI_ROWS; ++k) { lo += rlo[k]; up += rup[k]; }
-    double* p = part_ws + (pair * chunks + blockIdx.x) * 2;
-    p[0] = lo;
-    p[1] = up;
-    __threadfence();
-    last = atomicAdd(counters + pair, 1u) == (unsigned)chunks - 1u;
-  }
-  __syncthreads();
-  if (last && threadIdx.x == 0) {
-    __threadfence();
-    const double* p = part_ws + pair * chunks * 2;
-    double lo = 0.0, up = 0.0;
-    for (int k = 0; k < chunks; ++k) {
-      lo += __hip_atomic_load(p + 2 * k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      up += __hip_atomic_load(p + 2 * k + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    out[pair * 2] = lo / (double)n;
-    out[pair * 2 + 1] = up / (double)n;
-    counters[pair] = 0u;
-  }
+  const int g = blockIdx.z;
+#define DIB_CIRCUIT_BODY 3
+#include "dib_circuit_bodies.h"
+#undef DIB_CIRCUIT_BODY
+}
+
+// ---- R replicas per launch (dib_circuit_fwd_batched / _bwd_batched / _mi_bounds_batched) ----
+// The model's architecture does not depend on the circuit (u is 16 columns wide for every G), so replicas may differ in
+// circuit, truth table, G, seed and beta and still share a launch.  A workgroup belongs to one replica (a grid index), moves its
+// pointers to that replica's slices and runs the single kernel's body text on them (dib_circuit_bodies.h): the same Philox rows
+// (local to the replica), the same fixed-order sums, the replica's own arrival counters.  No workgroup waits on a workgroup of
+// another replica.  The per-replica scalars travel in the kernel arguments (host arrays at the entry points; uniform index: scalar
+// loads): at most DIB_CIRCUIT_BATCH replicas per launch, the host splits a larger ensemble.
+#define DIB_CIRCUIT_BATCH 64
+struct DibCircuitBatchArgs {
+  const uint32_t* tables;            // the replicas' truth tables, concatenated
+  const float* params;               // replica 0's flat parameters; sc = params + r * param_stride + sc_off
+  long long param_stride, sc_off;
+  int B; uint32_t step;
+  const int32_t* row_in; int32_t* rows; float* u; float* y; float* kl;   // forward: [R][B], [R][B], [R][B][16], [R][B], [R][17]
+  const float* g_u; float* grads; long long grad_stride;                 // backward: [R][B][16]; g_sc = grads + r * grad_stride + sc_off
+  uint64_t seeds[DIB_CIRCUIT_BATCH];
+  float beta[DIB_CIRCUIT_BATCH];
+  int table_off[DIB_CIRCUIT_BATCH];  // words
+  int G[DIB_CIRCUIT_BATCH];
+};
+
+// grid (the single forward's workgroups, replicas)
+__global__ void __launch_bounds__(256) dib_circuit_batched_fwd_kernel(DibCircuitBatchArgs ba) {
+  const long long rep = blockIdx.y;
+  const int G = ba.G[rep], B = ba.B;
+  const uint32_t* __restrict__ const table = ba.tables + ba.table_off[rep];
+  const float* __restrict__ const sc = ba.params + rep * ba.param_stride + ba.sc_off;
+  const uint64_t seed = ba.seeds[rep];
+  const uint32_t step = ba.step;
+  const float beta = ba.beta[rep];
+  const int32_t* __restrict__ const row_in = ba.row_in ? ba.row_in + rep * B : nullptr;
+  int32_t* __restrict__ const row_out = ba.rows + rep * B;
+  float* __restrict__ const u = ba.u + rep * B * DIB_CIRCUIT_LD;
+  float* __restrict__ const y = ba.y + rep * B;
+  float* __restrict__ const kl = ba.kl + rep * (DIB_CIRCUIT_MAX_GATES + 1);
+#define DIB_CIRCUIT_BODY 1
+#include "dib_circuit_bodies.h"
+#undef DIB_CIRCUIT_BODY
+}
+
+// grid (gates, replicas): the workgroups of gates a replica does not have exit
+__global__ void __launch_bounds__(256) dib_circuit_batched_bwd_kernel(DibCircuitBatchArgs ba) {
+  const long long rep = blockIdx.y;
+  const int g = blockIdx.x;
+  const int G = ba.G[rep], B = ba.B;
+  if (g >= G) return;
+  const uint32_t* __restrict__ const table = ba.tables + ba.table_off[rep];
+  const float* __restrict__ const sc = ba.params + rep * ba.param_stride + ba.sc_off;
+  const uint64_t seed = ba.seeds[rep];
+  const uint32_t step = ba.step;
+  const float beta = ba.beta[rep];
+  const int32_t* __restrict__ const rows = ba.rows + rep * B;
+  const float* __restrict__ const g_u = ba.g_u + rep * B * DIB_CIRCUIT_LD;
+  float* __restrict__ const g_sc = ba.grads + rep * ba.grad_stride + ba.sc_off;
+#define DIB_CIRCUIT_BODY 2
+#include "dib_circuit_bodies.h"
+#undef DIB_CIRCUIT_BODY
+}
+
+// grid (chunks of 64 points, batches, 16 x replicas): z = 16 r + g runs over the (replica, gate) pairs, those with g >= G_r exit.
+// Every replica has a workspace slice of the single kernel's layout at G = 16 (partials, then arrival counters) and writes
+// out [R][16][nb][2]; rows g >= G_r are not touched.
+struct DibCircuitMiBatchArgs {
+  const float* params; long long param_stride, sc_off;
+  const float* xs; int n, nb;        // [R][nb][n]
+  char* ws; long long ws_stride;     // bytes between the replicas' slices
+  double* out;
+  uint64_t seeds[DIB_CIRCUIT_BATCH];
+  int G[DIB_CIRCUIT_BATCH];
+};
+
+__global__ void __launch_bounds__(256) dib_circuit_batched_mi_kernel(DibCircuitMiBatchArgs ba) {
+  const long long rep = blockIdx.z >> 4;
+  const int g = blockIdx.z & 15;
+  const int G = ba.G[rep], n = ba.n, nb = ba.nb;
+  if (g >= G) return;
+  const float* __restrict__ const sc = ba.params + rep * ba.param_stride + ba.sc_off;
+  const float* __restrict__ const xs = ba.xs + rep * nb * n;
+  const uint64_t seed = ba.seeds[rep];
+  double* __restrict__ const part_ws = (double*)(ba.ws + rep * ba.ws_stride);
+  unsigned* __restrict__ const counters = (unsigned*)(part_ws + (long long)DIB_CIRCUIT_MAX_GATES * nb * gridDim.x * 2);
+  double* __restrict__ const out = ba.out + rep * DIB_CIRCUIT_MAX_GATES * nb * 2;
+#define DIB_CIRCUIT_BODY 3
+#include "dib_circuit_bodies.h"
+#undef DIB_CIRCUIT_BODY
 }

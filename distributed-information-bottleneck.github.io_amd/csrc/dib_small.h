@@ -823,9 +823,20 @@ __host__ __device__ __forceinline__ DibSmallIntLds<P> dib_small_int_lds(P o, int
   return m;
 }
 
+// Where the workgroup's network sits when ONE argument set serves several networks of one shape (the replicas of
+// dib_small_integration_batched_kernel), in elements: parameters, rows of the row buffers (U, GU, h, g, pred, g_pred, Y, a0),
+// the gradient target (head_gw / head_gb), the head workspace (partial_w / partial_l / sync) and sums3.  All zero - constants,
+// folded away - in every other kernel.
+// ONLY the head step's path honours a non-zero shift: input from U, rows addressed by position (row_idx == NULL), one workgroup
+// per tile.  The gathered input (DIB_SMALL_INT_POSENC_IN: X, row_idx), a row_idx for the labels and cluster mode (cl_sync, xh)
+// are NOT shifted and would address replica 0; the one caller that passes a shift, dib_mlp_small_head_step_batched, builds
+// its argument set without any of them (host/small.h mlp_small_head_args).
+struct DibSmallIntShift { long long params = 0, rows = 0, grads = 0, ws = 0, sums = 0; };
+
 // CLUSTER: workgroup `crank` of the a.cl that share `tile` (see above); else one workgroup per tile
 template <bool CLUSTER>
-__device__ __forceinline__ void dib_small_integration_body(const DibSmallIntArgs& a, const int tile, const int crank = 0) {
+__device__ __forceinline__ void dib_small_integration_body(const DibSmallIntArgs& a, const int tile, const int crank = 0,
+                                                           const DibSmallIntShift sh = DibSmallIntShift()) {
   constexpr int ROWS = DIB_SMALL_ROWS;
   const int cl = CLUSTER ? a.cl : 1;
   const bool clustered = CLUSTER;   // the slice primitives (a network of the paired grid may be a "cluster" of ONE workgroup per tile)
@@ -863,11 +874,11 @@ __device__ __forceinline__ void dib_small_integration_body(const DibSmallIntArgs
   float* const head_w = m.head_w;
   float* const head_y = m.head_y;
   if (a.mode & DIB_SMALL_INT_HEAD) {
-    for (int k = tid; k <= KL; k += DIB_SMALL_THREADS) head_w[k] = k < KL ? a.params[wo_off + k] : a.params[bo_off];
+    for (int k = tid; k <= KL; k += DIB_SMALL_THREADS) head_w[k] = k < KL ? (a.params + sh.params)[wo_off + k] : (a.params + sh.params)[bo_off];
     if (tid < ROWS && tid < rows_valid) {
       const int b = r0 + tid;
       const long long grow = a.row_idx ? (long long)a.row_idx[b] : a.row0 + b;
-      head_y[tid] = a.Y[grow * a.ldy];
+      head_y[tid] = a.Y[(sh.rows + grow) * a.ldy];
     }
   }
   if (a.mode & DIB_SMALL_INT_FWD) {
@@ -884,7 +895,7 @@ __device__ __forceinline__ void dib_small_integration_body(const DibSmallIntArgs
         }
         float* dst = us + row * pu + c;
         const bool keep = ok && a.a0 != nullptr && lead;
-        float* gd = a.a0 + (long long)(r0 + row) * a.K0 + c;
+        float* gd = a.a0 + (sh.rows + (r0 + row)) * a.K0 + c;
         dst[0] = x;
         if (keep) gd[0] = x;
         float fr = 2.0f;
@@ -896,7 +907,7 @@ __device__ __forceinline__ void dib_small_integration_body(const DibSmallIntArgs
         }
       }
     } else {
-      dib_small_load_tile(a.U + (long long)r0 * a.K0, a.K0, a.K0, rows_valid, us, pu);
+      dib_small_load_tile(a.U + (sh.rows + r0) * a.K0, a.K0, a.K0, rows_valid, us, pu);
     }
     __syncthreads();
     DIB_ST(17);
@@ -907,10 +918,10 @@ __device__ __forceinline__ void dib_small_integration_body(const DibSmallIntArgs
         const int K = l == 0 ? a.K0 : a.width[l > 0 ? l - 1 : 0], pin = l == 0 ? pu : ph[l > 0 ? l - 1 : 0];
         if (clustered) {
           // (one workgroup per tile and no stash: nothing leaves the CU)
-          float* const gx = (stash || multi) ? (stash ? a.h[l] : a.xh[l]) + (long long)r0 * a.width[l] : nullptr;
+          float* const gx = (stash || multi) ? (stash ? a.h[l] : a.xh[l]) + (sh.rows + r0) * a.width[l] : nullptr;
           int col0, ncols;
           dib_small_cluster_slice(a.width[l], crank, cl, col0, ncols);
-          dib_small_fwd_cols(in, pin, K, a.params + a.w_off[l], a.width[l], col0, ncols, a.params + a.b_off[l], slope, hs[l], ph[l],
+          dib_small_fwd_cols(in, pin, K, a.params + sh.params + a.w_off[l], a.width[l], col0, ncols, a.params + sh.params + a.b_off[l], slope, hs[l], ph[l],
                              gx, rows_valid, xch, l == 0 ? 6 : 45);
           DIB_ST(30 + l);
           if (multi) {
@@ -919,8 +930,8 @@ __device__ __forceinline__ void dib_small_integration_body(const DibSmallIntArgs
             __syncthreads();
           }
         } else {
-          dib_small_fwd(in, pin, K, K, a.params + a.w_off[l], a.width[l], a.params + a.b_off[l], slope, hs[l], ph[l],
-                        stash ? a.h[l] + (long long)r0 * a.width[l] : nullptr, a.width[l], rows_valid, xch);
+          dib_small_fwd(in, pin, K, K, a.params + sh.params + a.w_off[l], a.width[l], a.params + sh.params + a.b_off[l], slope, hs[l], ph[l],
+                        stash ? a.h[l] + (sh.rows + r0) * a.width[l] : nullptr, a.width[l], rows_valid, xch);
         }
         DIB_ST(18 + l);
       }
@@ -928,8 +939,8 @@ __device__ __forceinline__ void dib_small_integration_body(const DibSmallIntArgs
   } else if (a.mode & DIB_SMALL_INT_LOAD_H) {
 #pragma unroll
     for (int l = 0; l < 3; ++l)
-      if (l < n) dib_small_load_tile(a.h[l] + (long long)r0 * a.width[l], a.width[l], a.width[l], rows_valid, hs[l], ph[l]);
-    if (a.mode & DIB_SMALL_INT_LOAD_G) dib_small_load_tile(g_last + (long long)r0 * KL, KL, KL, rows_valid, gl, pl);
+      if (l < n) dib_small_load_tile(a.h[l] + (sh.rows + r0) * a.width[l], a.width[l], a.width[l], rows_valid, hs[l], ph[l]);
+    if (a.mode & DIB_SMALL_INT_LOAD_G) dib_small_load_tile(g_last + (sh.rows + r0) * KL, KL, KL, rows_valid, gl, pl);
     __syncthreads();
   }
 
@@ -937,11 +948,11 @@ __device__ __forceinline__ void dib_small_integration_body(const DibSmallIntArgs
     if (clustered) {   // its columns go straight to pred: nothing to exchange
       int col0, ncols;
       dib_small_cluster_slice(a.out_dim, crank, cl, col0, ncols);
-      dib_small_fwd_cols(hl, pl, KL, a.params + wo_off, a.out_dim, col0, ncols, a.params + bo_off, dib_neg_slope(a.out_act), nullptr, 0,
-                         a.pred + (long long)r0 * a.out_dim, rows_valid, xch);
+      dib_small_fwd_cols(hl, pl, KL, a.params + sh.params + wo_off, a.out_dim, col0, ncols, a.params + sh.params + bo_off, dib_neg_slope(a.out_act), nullptr, 0,
+                         a.pred + (sh.rows + r0) * a.out_dim, rows_valid, xch);
     } else {
-      dib_small_fwd(hl, pl, KL, KL, a.params + wo_off, a.out_dim, a.params + bo_off, dib_neg_slope(a.out_act), nullptr, 0,
-                    a.pred + (long long)r0 * a.out_dim, a.out_dim, rows_valid, xch);
+      dib_small_fwd(hl, pl, KL, KL, a.params + sh.params + wo_off, a.out_dim, a.params + sh.params + bo_off, dib_neg_slope(a.out_act), nullptr, 0,
+                    a.pred + (sh.rows + r0) * a.out_dim, a.out_dim, rows_valid, xch);
     }
   }
 
@@ -996,8 +1007,8 @@ __device__ __forceinline__ void dib_small_integration_body(const DibSmallIntArgs
       if (lane == 0 && ok2[r]) {
         const int b = r0 + wave + 8 * r;
         if (lead) {
-          a.pred[b] = z;
-          if (grad) a.g_pred[b] = gg;
+          a.pred[sh.rows + b] = z;
+          if (grad) a.g_pred[sh.rows + b] = gg;
         }
         lsum += l;
         correct += ((z > 0.5f ? 1.f : 0.f) == yy) ? 1.f : 0.f;
@@ -1017,7 +1028,7 @@ __device__ __forceinline__ void dib_small_integration_body(const DibSmallIntArgs
               const float hv = hl[row * pl + k];
               const float gv = gg2[r] * w * dib_small_act_grad(slope, hv);
               gl[row * pl + k] = gv;
-              if (lead) g_last[(long long)(r0 + row) * KL + k] = gv;
+              if (lead) g_last[(sh.rows + (r0 + row)) * KL + k] = gv;
               pw[c] += hv * gg2[r];
             }
         }
@@ -1036,7 +1047,7 @@ __device__ __forceinline__ void dib_small_integration_body(const DibSmallIntArgs
     if (lane == 0) { redw[wave * (KL + 1) + KL] = pb; redl[2 * wave] = lsum; redl[2 * wave + 1] = correct; }
     __syncthreads();
     if (grad && lead) {
-      float* dst = a.partial_w + (long long)tile * (KL + 1);
+      float* dst = a.partial_w + sh.ws + (long long)tile * (KL + 1);
       for (int i = tid; i <= KL; i += DIB_SMALL_THREADS) {
         float t = 0.f;
 #pragma unroll
@@ -1048,25 +1059,25 @@ __device__ __forceinline__ void dib_small_integration_body(const DibSmallIntArgs
       float t = 0.f;
 #pragma unroll
       for (int w = 0; w < 8; ++w) t += redl[2 * w + tid];
-      a.partial_l[2 * tile + tid] = t;
+      a.partial_l[sh.ws + (2 * tile + tid)] = t;
     }
   }
 
   DIB_ST(22);
   if (a.mode & DIB_SMALL_INT_BWD_OUT) {   // dL/dh_{n-1} from a given dL/dpred (custom loss: InfoNCE, train.py:216-219)
-    dib_small_load_tile(a.g_pred + (long long)r0 * a.out_dim, a.out_dim, a.out_dim, rows_valid, ps, po);
+    dib_small_load_tile(a.g_pred + (sh.rows + r0) * a.out_dim, a.out_dim, a.out_dim, rows_valid, ps, po);
     __syncthreads();
     if (clustered) {
       int k0, kc;
       dib_small_cluster_slice(KL, crank, cl, k0, kc);
-      dib_small_bwd_cols(ps, po, a.out_dim, a.params + wo_off, KL, k0, kc, hl, pl, slope, gl, pl, g_last + (long long)r0 * KL, rows_valid, xch);
+      dib_small_bwd_cols(ps, po, a.out_dim, a.params + sh.params + wo_off, KL, k0, kc, hl, pl, slope, gl, pl, g_last + (sh.rows + r0) * KL, rows_valid, xch);
       if (multi) {
         dib_small_cluster_exchange(clw, 3, cl, cl_same);
-        dib_small_load_tile(g_last + (long long)r0 * KL, KL, KL, rows_valid, gl, pl);
+        dib_small_load_tile(g_last + (sh.rows + r0) * KL, KL, KL, rows_valid, gl, pl);
         __syncthreads();
       }
     } else {
-      dib_small_bwd(ps, po, a.out_dim, a.params + wo_off, KL, hl, pl, slope, gl, pl, g_last + (long long)r0 * KL, KL, rows_valid, xch);
+      dib_small_bwd(ps, po, a.out_dim, a.params + sh.params + wo_off, KL, hl, pl, slope, gl, pl, g_last + (sh.rows + r0) * KL, KL, rows_valid, xch);
     }
   }
 
@@ -1076,10 +1087,10 @@ __device__ __forceinline__ void dib_small_integration_body(const DibSmallIntArgs
     for (int l = 2; l >= 1; --l) {   // dL/dh_{l-1} = (dL/dh_l @ W_l^T) (.) act'(h_{l-1})
       if (l < n) {
         if (clustered) {
-          float* const gx = a.g[l - 1] + (long long)r0 * a.width[l - 1];
+          float* const gx = a.g[l - 1] + (sh.rows + r0) * a.width[l - 1];
           int k0, kc;
           dib_small_cluster_slice(a.width[l - 1], crank, cl, k0, kc);
-          dib_small_bwd_cols(gs[l], ph[l], a.width[l], a.params + a.w_off[l], a.width[l - 1], k0, kc, hs[l - 1], ph[l - 1], slope,
+          dib_small_bwd_cols(gs[l], ph[l], a.width[l], a.params + sh.params + a.w_off[l], a.width[l - 1], k0, kc, hs[l - 1], ph[l - 1], slope,
                              gs[l - 1], ph[l - 1], gx, rows_valid, xch, 34);
           DIB_ST(32 + l);
           if (multi) {
@@ -1088,8 +1099,8 @@ __device__ __forceinline__ void dib_small_integration_body(const DibSmallIntArgs
             __syncthreads();
           }
         } else {
-          dib_small_bwd(gs[l], ph[l], a.width[l], a.params + a.w_off[l], a.width[l - 1], hs[l - 1], ph[l - 1], slope, gs[l - 1],
-                        ph[l - 1], a.g[l - 1] + (long long)r0 * a.width[l - 1], a.width[l - 1], rows_valid, xch);
+          dib_small_bwd(gs[l], ph[l], a.width[l], a.params + sh.params + a.w_off[l], a.width[l - 1], hs[l - 1], ph[l - 1], slope, gs[l - 1],
+                        ph[l - 1], a.g[l - 1] + (sh.rows + r0) * a.width[l - 1], a.width[l - 1], rows_valid, xch);
         }
         DIB_ST(24 + l);
       }
@@ -1099,11 +1110,11 @@ __device__ __forceinline__ void dib_small_integration_body(const DibSmallIntArgs
       if (clustered) {
         int k0, kc;
         dib_small_cluster_slice(a.K0, crank, cl, k0, kc);
-        dib_small_bwd_cols(gs[0], ph[0], a.width[0], a.params + a.w_off[0], a.K0, k0, kc, nullptr, 0, 1.f, nullptr, 0,
-                           a.GU + (long long)r0 * a.K0, rows_valid, xch, 51);
+        dib_small_bwd_cols(gs[0], ph[0], a.width[0], a.params + sh.params + a.w_off[0], a.K0, k0, kc, nullptr, 0, 1.f, nullptr, 0,
+                           a.GU + (sh.rows + r0) * a.K0, rows_valid, xch, 51);
       } else {
-        dib_small_bwd(gs[0], ph[0], a.width[0], a.params + a.w_off[0], a.K0, nullptr, 0, 1.f, nullptr, 0,
-                      a.GU + (long long)r0 * a.K0, a.K0, rows_valid, xch);
+        dib_small_bwd(gs[0], ph[0], a.width[0], a.params + sh.params + a.w_off[0], a.K0, nullptr, 0, 1.f, nullptr, 0,
+                      a.GU + (sh.rows + r0) * a.K0, a.K0, rows_valid, xch);
       }
     }
     DIB_ST(28);
@@ -1117,8 +1128,8 @@ __device__ __forceinline__ void dib_small_integration_body(const DibSmallIntArgs
     __syncthreads();
     if (tid == 0) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      const bool last = __hip_atomic_fetch_add(a.sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-      if (last) __hip_atomic_store(a.sync, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const bool last = __hip_atomic_fetch_add(a.sync + sh.ws, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+      if (last) __hip_atomic_store(a.sync + sh.ws, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       s_last = last;
     }
     __syncthreads();
@@ -1127,14 +1138,14 @@ __device__ __forceinline__ void dib_small_integration_body(const DibSmallIntArgs
     const int ntl = (int)gridDim.x;
     for (int i = tid; i <= KL; i += DIB_SMALL_THREADS) {
       float t = 0.f;
-      for (int tl = 0; tl < ntl; ++tl) t += a.partial_w[(long long)tl * (KL + 1) + i];
-      if (i < KL) a.head_gw[i] = t; else a.head_gb[0] = t;
+      for (int tl = 0; tl < ntl; ++tl) t += a.partial_w[sh.ws + (long long)tl * (KL + 1) + i];
+      if (i < KL) a.head_gw[sh.grads + i] = t; else a.head_gb[sh.grads] = t;
     }
     if (tid < 2) {
       float t = 0.f;
-      for (int tl = 0; tl < ntl; ++tl) t += a.partial_l[2 * tl + tid];
-      a.sums3[tid] = t;
-      if (tid == 0) a.sums3[2] = t * a.loss_scale;
+      for (int tl = 0; tl < ntl; ++tl) t += a.partial_l[sh.ws + (2 * tl + tid)];
+      a.sums3[sh.sums + tid] = t;
+      if (tid == 0) a.sums3[sh.sums + 2] = t * a.loss_scale;
     }
   }
 }
@@ -1162,6 +1173,28 @@ dib_small_integration_pair_kernel(DibSmallIntPair p) {
   const DibSmallIntArgs& a = p.s[blockIdx.y];
   if ((int)blockIdx.x * DIB_SMALL_ROWS >= a.batch) return;   // the two batches may differ
   dib_small_integration_body<false>(a, blockIdx.x);
+}
+
+// R replicas of ONE network shape in one grid (dib_mlp_small_head_step_batched): blockIdx.y is the replica, blockIdx.x its row
+// tile.  The kernel arguments hold replica 0's argument set - it stays in the kernarg segment, read with scalar loads - and the
+// distances between replicas; a workgroup hands the body its replica's DibSmallIntShift (block-uniform scalar products) and the
+// single-workgroup body adds it where it forms a global address - never cluster mode.  The rows' buffers are replica-major
+// ([R][batch][width]), the parameters, the gradient target and the head workspace (partials + the self-cleaning arrival word)
+// sit at a replica stride, so "the last workgroup to arrive" (gridDim.x of them) is per replica and no workgroup waits on
+// another replica's.  (A moved COPY of the argument set is no alternative: the body indexes its arrays with the layer, and
+// the copy - 392 bytes - lands in scratch.)
+struct DibSmallIntBatch {
+  DibSmallIntArgs a;                 // replica 0
+  long long param_stride;            // floats between the replicas' parameters
+  long long grad_stride;             // ... between their gradient targets (head_gw / head_gb)
+  long long ws_stride;               // ... between their head workspaces (partial_w / partial_l / sync)
+};
+__global__ void __launch_bounds__(DIB_SMALL_THREADS)
+dib_small_integration_batched_kernel(DibSmallIntBatch p) {
+  const long long r = blockIdx.y;
+  DibSmallIntShift sh;
+  sh.params = r * p.param_stride; sh.rows = r * p.a.batch; sh.grads = r * p.grad_stride; sh.ws = r * p.ws_stride; sh.sums = r * 3;
+  dib_small_integration_body<false>(p.a, blockIdx.x, 0, sh);
 }
 
 // ... and the paired grid in cluster mode: each network with its own cluster size (s[i].cl; 1 = one workgroup per tile on the slice

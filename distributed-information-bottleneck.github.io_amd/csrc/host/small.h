@@ -189,13 +189,13 @@ int64_t dib_mlp_small_head_workspace_bytes(const dib_mlp_desc* d, int n) {
   if (!d || n < 1 || d->n_hidden < 1 || d->n_hidden > 3) return DIB_E_ARG;
   return ((int64_t)small_tiles(n) * (d->width[d->n_hidden - 1] + 1 + 2) + 16) * (int64_t)sizeof(float);
 }
-int dib_mlp_small_head_step(const dib_mlp_desc* d, const float* params, const float* x, int n, const float* y, int64_t ldy,
-                            int loss_kind, float inv_global_batch, float* const* h, float* const* g, float* pred, float* g_pred,
-                            float* g_x, float* grads, float* sums3, void* ws, dib_stream_t stream) {
+// the head step's argument set on (one replica's) buffers; DIB_OK or the entry point's error.  ws: partials, then the arrival word
+static int mlp_small_head_args(const dib_mlp_desc* d, const float* params, const float* x, int n, const float* y, int64_t ldy,
+                               int loss_kind, float inv_global_batch, float* const* h, float* const* g, float* pred, float* g_pred,
+                               float* g_x, float* grads, float* sums3, void* ws, DibSmallIntArgs& a) {
   if (!d || !params || !x || !y || !h || !g || !pred || !g_pred || !grads || !sums3 || !ws || n <= 0) return DIB_E_ARG;
   if (loss_kind != DIB_LOSS_BCE_LOGITS && loss_kind != DIB_LOSS_MSE) return DIB_E_UNSUPPORTED;
   if (!dib_mlp_small_head_supported(d, n)) return DIB_E_UNSUPPORTED;
-  DibSmallIntArgs a;
   std::memset(&a, 0, sizeof(a));
   a.mode = DIB_SMALL_INT_FWD | DIB_SMALL_INT_HEAD | DIB_SMALL_INT_HEAD_GRAD | DIB_SMALL_INT_BWD | DIB_SMALL_INT_HEAD_REDUCE |
            (g_x ? 0 : DIB_SMALL_INT_NO_GU);
@@ -213,9 +213,45 @@ int dib_mlp_small_head_step(const dib_mlp_desc* d, const float* params, const fl
   a.sync = (unsigned*)(a.partial_l + 2 * tiles);   // zero at first use (the caller zero-fills the workspace once)
   a.head_gw = grads + d->w_off[d->n_hidden]; a.head_gb = grads + d->b_off[d->n_hidden];
   a.sums3 = sums3; a.loss_scale = inv_global_batch;
+  return DIB_OK;
+}
+int dib_mlp_small_head_step(const dib_mlp_desc* d, const float* params, const float* x, int n, const float* y, int64_t ldy,
+                            int loss_kind, float inv_global_batch, float* const* h, float* const* g, float* pred, float* g_pred,
+                            float* g_x, float* grads, float* sums3, void* ws, dib_stream_t stream) {
+  DibSmallIntArgs a;
+  if (int rc = mlp_small_head_args(d, params, x, n, y, ldy, loss_kind, inv_global_batch, h, g, pred, g_pred, g_x, grads, sums3, ws, a))
+    return rc;
   const size_t lds = mlp_small_lds(d, true);
   ProfScope ps(kProfOther, (hipStream_t)stream);
-  return launch_lds<&dib_small_integration_kernel>(dim3(tiles), dim3(DIB_SMALL_THREADS), lds, (hipStream_t)stream, a);
+  return launch_lds<&dib_small_integration_kernel>(dim3(small_tiles(n)), dim3(DIB_SMALL_THREADS), lds, (hipStream_t)stream, a);
+}
+
+// ---- R replicas of the head step in ONE launch (csrc/dib_small.h dib_small_integration_batched_kernel): grid (row tiles, R) ----
+int dib_mlp_small_head_batched_supported(const dib_mlp_desc* d, int n, int replicas) {
+  return replicas >= 1 && replicas <= 65535 && dib_mlp_small_head_supported(d, n) ? 1 : 0;
+}
+// floats between the replicas' workspace slices: the single entry's workspace, rounded up to 64 bytes
+static int64_t mlp_small_head_ws_stride(const dib_mlp_desc* d, int n) {
+  return align_up(dib_mlp_small_head_workspace_bytes(d, n), 64) / (int64_t)sizeof(float);
+}
+int64_t dib_mlp_small_head_batched_workspace_bytes(const dib_mlp_desc* d, int n, int replicas) {
+  if (!d || n < 1 || replicas < 1 || d->n_hidden < 1 || d->n_hidden > 3) return DIB_E_ARG;
+  return (int64_t)replicas * mlp_small_head_ws_stride(d, n) * (int64_t)sizeof(float);
+}
+int dib_mlp_small_head_step_batched(const dib_mlp_desc* d, const float* params, int64_t param_stride, const float* x, int n,
+                                    int replicas, const float* y, int64_t ldy, int loss_kind, float inv_global_batch,
+                                    float* const* h, float* const* g, float* pred, float* g_pred, float* g_x, float* grads,
+                                    int64_t grad_stride, float* sums3, void* ws, dib_stream_t stream) {
+  if (param_stride < 0 || grad_stride < 0) return DIB_E_ARG;
+  DibSmallIntBatch p;
+  if (int rc = mlp_small_head_args(d, params, x, n, y, ldy, loss_kind, inv_global_batch, h, g, pred, g_pred, g_x, grads, sums3, ws, p.a))
+    return rc;
+  if (!dib_mlp_small_head_batched_supported(d, n, replicas)) return DIB_E_UNSUPPORTED;
+  p.param_stride = param_stride; p.grad_stride = grad_stride; p.ws_stride = mlp_small_head_ws_stride(d, n);
+  const size_t lds = mlp_small_lds(d, true);
+  ProfScope ps(kProfOther, (hipStream_t)stream);
+  return launch_lds<&dib_small_integration_batched_kernel>(dim3(small_tiles(n), replicas), dim3(DIB_SMALL_THREADS), lds,
+                                                           (hipStream_t)stream, p);
 }
 
 int dib_integration_fwd_and_mlp_fwd(dib_layout* l, int batch, const float* params, void* ws, const dib_mlp_desc* d,

@@ -43,6 +43,35 @@ int64_t dib_circuit_mi_workspace_bytes(int G, int n, int nb);
 int dib_circuit_mi_bounds(const float* sc, int G, const float* x, int n, int nb, uint64_t seed, double* out, void* ws,
                           dib_stream_t stream);
 
+/* ---- R replicas per launch (CircuitEnsemble) ----
+ * The model's shapes do not depend on the circuit (u is 16 columns wide for every G), so R models that differ in circuit, G,
+ * seed and beta share every launch: the replica is a grid index, each workgroup runs the single kernel's code on its
+ * replica's slices, and every output of replica r has the bits of the single entry point called on those slices.
+ * Replica r's scalars are params + r * param_stride + sc_off (s[0..G_r) then lv[0..G_r)); G, table_off, seeds and beta are HOST
+ * arrays of R entries (they travel in the kernel arguments, 64 replicas per launch: a larger ensemble takes ceil(R / 64)
+ * launches).  tables: the R packed truth tables in one device buffer of table_words words, replica r's 2^G_r words at
+ * table_off[r].  A refusal (R < 1, any G_r or B outside the envelope: DIB_E_UNSUPPORTED; a NULL pointer, a negative stride, a
+ * table outside the buffer: DIB_E_ARG) launches nothing. */
+int dib_circuit_batched_supported(const int* G, int replicas, int B);
+/* row_idx [R][B] or NULL; rows_out [R][B], u [R][B][16], y [R][B], kl [R][17] (replica r: {KL_0 .. KL_{G_r-1}, beta_r sum KL},
+ * the rest of its row untouched). */
+int dib_circuit_fwd_batched(const uint32_t* tables, int64_t table_words, const int64_t* table_off, const int* G, int replicas, int B,
+                            const float* params, int64_t param_stride, int64_t sc_off, const uint64_t* seeds, uint32_t step,
+                            const float* beta, const int32_t* row_idx, int32_t* rows_out, float* u, float* y, float* kl,
+                            dib_stream_t stream);
+/* rows [R][B], g_u [R][B][16]; the 2 G_r gradients of replica r go to grads + r * grad_stride + sc_off.  Grid (gate, replica):
+ * the same float64 fixed-order sums as dib_circuit_bwd. */
+int dib_circuit_bwd_batched(const uint32_t* tables, int64_t table_words, const int64_t* table_off, const int* G, int replicas, int B,
+                            const float* params, int64_t param_stride, int64_t sc_off, const uint64_t* seeds, uint32_t step,
+                            const float* beta, const int32_t* rows, const float* g_u, float* grads, int64_t grad_stride,
+                            dib_stream_t stream);
+/* x [R][nb][n]; out [R][16][nb][2], rows g >= G_r untouched; ws: dib_circuit_mi_batched_workspace_bytes (one slice per replica),
+ * zero-filled once by the caller. */
+int64_t dib_circuit_mi_batched_workspace_bytes(int replicas, int n, int nb);
+int dib_circuit_mi_bounds_batched(const float* params, int64_t param_stride, int64_t sc_off, const int* G, int replicas,
+                                  const float* x, int n, int nb, const uint64_t* seeds, double* out, void* ws,
+                                  dib_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

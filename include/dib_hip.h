@@ -396,6 +396,17 @@ int64_t dib_mlp_small_head_workspace_bytes(const dib_mlp_desc* d, int n);
 int dib_mlp_small_head_step(const dib_mlp_desc* d, const float* params, const float* x, int n, const float* y, int64_t ldy,
                             int loss_kind, float inv_global_batch, float* const* h, float* const* g, float* pred, float* g_pred,
                             float* g_x, float* grads, float* sums3, void* ws, dib_stream_t stream);
+/* ... and R replicas of it in ONE launch, grid (row tiles, R): one descriptor, replica r's parameters at params + r *
+ * param_stride and its output-layer gradient at grads + r * grad_stride + w_off / b_off[n_hidden]; x, y ([R][n] rows of ldy),
+ * h[i], g[i], pred, g_pred and g_x are replica-major ([R][n][width]), sums3 is [R][3].  Every replica has its own workspace
+ * slice (partials and arrival word), so each output has the bits of dib_mlp_small_head_step on that replica's slices.
+ * supported: the single entry's rule and 1 <= replicas <= 65535. */
+int dib_mlp_small_head_batched_supported(const dib_mlp_desc* d, int n, int replicas);
+int64_t dib_mlp_small_head_batched_workspace_bytes(const dib_mlp_desc* d, int n, int replicas);
+int dib_mlp_small_head_step_batched(const dib_mlp_desc* d, const float* params, int64_t param_stride, const float* x, int n,
+                                    int replicas, const float* y, int64_t ldy, int loss_kind, float inv_global_batch,
+                                    float* const* h, float* const* g, float* pred, float* g_pred, float* g_x, float* grads,
+                                    int64_t grad_stride, float* sums3, void* ws, dib_stream_t stream);
 /* The custom loop runs TWO independent networks between the encoder bank and the loss, and again between the loss and the
  * encoder bank's backward (train.py:203-219: model(x) and output_encoder(y); tape.gradient of both).  At its batch sizes
  * each of them is a handful of workgroups, so the two entry points below give the pairs ONE grid each:

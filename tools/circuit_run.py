@@ -5,7 +5,9 @@ per-gate information (bits, smoothed as cell 6 does), the exhaustive Shapley val
 (dib_amd.subset_information: one launch for all subsets), every selected subset's information and rank among the subsets of its
 size (cell 7's check), the group-order check of the paper circuit against the notebook's printed sequence, and the smoothed
 curves.  --subset_information True also writes subset_information_<circuit>/subset_information.npz and cell 7's figure.
-    python tools/circuit_run.py [--out-dir profiles] [--only fig1|si] [--seed 0] [--subset_information True]
+--ensemble trains the six SI circuits in lockstep on one CircuitEnsemble (every launch of a step shared) and writes the same
+records; replica k has the seeds and draws of the sequential run of circuit k, "fit_wall_s" is the shared wall time.
+    python tools/circuit_run.py [--out-dir profiles] [--only fig1|si] [--seed 0] [--subset_information True] [--ensemble]
 """
 import argparse
 import importlib.util
@@ -30,6 +32,28 @@ def run_one(name, spec, beta_end, seed, steps=50_000, batch_size=512, subset_inf
     t0 = time.perf_counter()
     h = m.fit(table, number_training_steps=steps, batch_size=batch_size, beta_start=1e-3, beta_end=beta_end, seed=seed)
     wall = time.perf_counter() - t0
+    return record(name, spec, beta_end, seed, h, wall, steps, batch_size, subset_information_dir)
+
+
+def run_ensemble(jobs, seed, steps=50_000, batch_size=512, subset_information_dir=None):
+    """the jobs' circuits as the replicas of one CircuitEnsemble: [(name, record)] in the jobs' order"""
+    from dib_amd import circuit
+    R = len(jobs)
+    ens = circuit.CircuitEnsemble([circuit.truth_table(spec) for _, spec, _ in jobs], init_seeds=[seed] * R, noise_seeds=[seed] * R)
+    t0 = time.perf_counter()
+    hs = ens.fit(number_training_steps=steps, batch_size=batch_size, beta_start=1e-3, beta_end=[b for _, _, b in jobs],
+                 seeds=[seed] * R)
+    wall = time.perf_counter() - t0
+    return [(name, record(name, spec, beta_end, seed, h, wall, steps, batch_size,
+                          subset_information_dir(name) if subset_information_dir else None))
+            for (name, spec, beta_end), h in zip(jobs, hs)]
+
+
+def record(name, spec, beta_end, seed, h, wall, steps, batch_size, subset_information_dir=None):
+    """the JSON record of one circuit's fit history h"""
+    from dib_amd import circuit, subset_information
+    table = circuit.truth_table(spec)
+    G = table.shape[1] - 1
     hy = circuit.entropy_bits(table[:, -1])
     ip = circuit.information_plane(h, hy)
     seq = [list(map(int, s)) for s in circuit.selected_subsets(ip["info_in_parts"])[:-1]]
@@ -60,6 +84,8 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--subset_information", type=lambda v: str(v).lower() in ("1", "true", "yes", "y", "t"), default=False,
                     help="write subset_information.npz (masks, bits, entropy_y_bits, Shapley values) and cell 7's figure per circuit")
+    ap.add_argument("--ensemble", action="store_true", help="the SI circuits as one CircuitEnsemble trained in lockstep")
+    ap.add_argument("--steps", type=int, default=50_000)
     a = ap.parse_args(argv)
     from dib_amd import circuit
     os.makedirs(a.out_dir, exist_ok=True)
@@ -68,9 +94,13 @@ def main(argv=None):
         jobs.append(("fig1", circuit.PAPER_CIRCUIT, 5.0))
     if a.only in (None, "si"):
         jobs += [(f"si_{'abcdef'[k]}", s, 1.0) for k, s in enumerate(circuit.SI_CIRCUITS)]
+    sub_dir = (lambda name: os.path.join(a.out_dir, f"subset_information_{name}")) if a.subset_information else None
+    lockstep = {}
+    if a.ensemble:
+        lockstep = dict(run_ensemble([j for j in jobs if j[0] != "fig1"], a.seed, steps=a.steps, subset_information_dir=sub_dir))
     for name, spec, beta_end in jobs:
-        rec = run_one(name, spec, beta_end, a.seed,
-                      subset_information_dir=os.path.join(a.out_dir, f"subset_information_{name}") if a.subset_information else None)
+        rec = lockstep.get(name) or run_one(name, spec, beta_end, a.seed, steps=a.steps,
+                                            subset_information_dir=sub_dir(name) if sub_dir else None)
         if name == "fig1":
             sp = importlib.util.spec_from_file_location("paper_circuit_run", os.path.join(ROOT, "tools", "paper_circuit_run.py"))
             pcr = importlib.util.module_from_spec(sp)

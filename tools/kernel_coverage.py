@@ -61,6 +61,12 @@ ORACLE_TESTS = {
     "test_gpu_circuit.py": {
         "test_drawn_rows_eps_and_u_match_oracle", "test_step_bce_kl_and_all_gradients_match_oracle",
         "test_thirty_adam_steps_through_the_beta_ramp_match_oracle", "test_mi_bounds_match_compute_batch_and_the_per_gate_loop"},
+    "test_gpu_circuit_batched_kernels.py": {
+        "test_fwd_and_bwd_batched_equal_the_single_kernels_and_the_oracle",
+        "test_head_step_batched_equals_the_single_entry_and_a_float64_forward",
+        "test_mi_bounds_batched_equal_the_single_kernel_and_compute_batch"},
+    "test_gpu_circuit_ensemble.py": {
+        "test_step_of_every_replica_matches_oracle", "test_thirty_adam_steps_through_per_replica_beta_ramps_match_oracle"},
     "test_gpu_random_partition.py": {
         "test_kernel_matches_oracle_across_the_envelope", "test_duplicated_and_negated_columns_go_to_the_lower_index",
         "test_notebook_configurations_match_the_oracle", "test_logistic_generating_partition_known_answer"},
@@ -171,6 +177,10 @@ EQUIVALENCE_TESTS = {
     "test_gpu_measurement_ensemble.py": {
         "test_a_replica_does_not_see_the_others", "test_fit_retires_replicas_at_their_own_thresholds",
         "test_one_replica_as_a_model_and_its_symbols"},
+    "test_gpu_circuit_batched_kernels.py": {"test_65_replicas_in_two_launches_equal_65_single_calls"},
+    "test_gpu_circuit_ensemble.py": {
+        "test_one_replica_equals_the_single_model_bit_for_bit", "test_a_replica_does_not_see_the_others",
+        "test_fit_is_reproducible_and_evaluates_like_the_single_model", "test_to_model_continues_a_replica_with_the_same_bits"},
     "test_gpu_ctw_levels.py": {
         "test_chunks_do_not_change_the_bits_and_an_overflowing_window_goes_to_the_host",
         "test_entropy_rate_fit_on_the_device_backend", "test_random_partition_characterize_keeps_the_symbols_on_the_device"},
@@ -304,9 +314,11 @@ def merge(out_path, *part_paths):
     launches and test counts add up, the test lines are re-sorted together ('*' first) and cut to 12 again - every part lists
     its own first 12 in that order, so the merged first 12 are among them."""
     import re
-    kernels, order, dispatches, unassigned, other = {}, [], 0, 0, 0
+    kernels, order, dispatches, unassigned, other, n_parts = {}, [], 0, 0, 0, 0
     for path in part_paths:
         cur = None
+        merged = [int(m.group(1)) for m in (re.search(r", (\d+) parts of the suite merged;", l) for l in open(path)) if m]
+        n_parts += merged[0] if merged else 1     # (a record that is itself a merge counts with all its parts)
         for line in open(path):
             line = line.rstrip("\n")
             m = re.match(r"# test ranges from: .*; (\d+) dispatches, (\d+) outside", line)
@@ -329,7 +341,7 @@ def merge(out_path, *part_paths):
             elif not line.startswith("    "):
                 cur = None
     lines = ["# kernel coverage of `python -m pytest tests -m gpu` under rocprofv3 --kernel-trace --marker-trace -M",
-             f"# test ranges from: ROCTx ranges (rocprofv3 --marker-trace), {len(part_paths)} parts of the suite merged; {dispatches} dispatches, "
+             f"# test ranges from: ROCTx ranges (rocprofv3 --marker-trace), {n_parts} parts of the suite merged; {dispatches} dispatches, "
              f"{unassigned} outside every test range (session set-up)",
              f"# {len(order)} kernel symbols in libdib_hip.so (gfx950 code object); '*' = the test compares with the float64 / NumPy oracle,",
              "# '=' = the test demands equality (bits or fp32 summation-order tolerance) with a path that '*' tests check",

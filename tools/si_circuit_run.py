@@ -1,5 +1,8 @@
 """Science-level check: DIB on SI circuit (c) of the reference notebook (Boolean_circuits.ipynb:987-992):
-Y = AND(XOR(AND(x2,x0), x3), x1); Shapley values [0.096, 0.377, 0.096, 0.242]; H(Y) = 0.811 bits."""
+Y = AND(XOR(AND(x2,x0), x3), x1); Shapley values [0.096, 0.377, 0.096, 0.242]; H(Y) = 0.811 bits.
+    python tools/si_circuit_run.py --ensemble [--out-dir profiles] [--seed 0]
+trains the six Fig. S1 circuits in lockstep on one CircuitEnsemble instead and writes the records of the sequential path
+(tools/circuit_run.py --only si: profiles/circuit_run_si_[a-f].json)."""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -25,6 +28,13 @@ def run(epochs_pre=100, epochs_anneal=500, seed=0):
 
 
 if __name__ == "__main__":
+    if "--ensemble" in sys.argv[1:]:
+        import importlib.util
+        _spec = importlib.util.spec_from_file_location("circuit_run", os.path.join(os.path.dirname(os.path.abspath(__file__)), "circuit_run.py"))
+        _cr = importlib.util.module_from_spec(_spec)
+        _spec.loader.exec_module(_cr)
+        _cr.main(["--only", "si"] + sys.argv[1:])
+        sys.exit(0)
     kl, loss, acc, beta = run()
     for e in (0, 50, 99, 150, 250, 350, 450, 520, 560, 599):
         print(e, f"beta={beta[e]:.4f}", "KL bits", np.round(kl[e], 3), f"loss={loss[e]:.3f} acc={acc[e]:.3f}")
