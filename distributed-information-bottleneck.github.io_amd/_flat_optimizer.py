@@ -1,5 +1,6 @@
 """FlatOptimizer: the optimizer state over ONE flat parameter buffer (the slots of include/dib_optimizers.h, step count, learning
-rate, bound rule) and the launches that read and write it: HipEngine and DenseStack each hold one.  The parameters and gradients
+rate, bound rule) and the launches that read and write it: HipEngine, DenseStack, the measurement models and the circuit models
+each hold one.  The parameters and gradients
 are the caller's: every step takes them as arguments (MeasurementIB rebinds its stacks' buffers to views of one allocation)."""
 from __future__ import annotations
 
@@ -23,9 +24,11 @@ def _key(opt):
 
 
 class FlatOptimizer:
-    def __init__(self, lib, stream, n_alloc: int, device, learning_rate: float = 1e-3):
+    def __init__(self, lib, stream, n_alloc: int, device, learning_rate: float = 1e-3, m=None, v=None):
+        """m, v: the caller's own zeroed tensors of n_alloc floats (views of a larger allocation) in place of fresh ones; every
+        method, reset() and bind() included, works on them where they lie"""
         self.lib, self._stream = lib, stream
-        self.m, self.v = (torch.zeros(n_alloc, dtype=torch.float32, device=device) for _ in range(2))
+        self.m, self.v = (t if t is not None else torch.zeros(n_alloc, dtype=torch.float32, device=device) for t in (m, v))
         self.s2: Optional[torch.Tensor] = None        # third slot (AMSGrad's vhat, RMSprop centred with momentum)
         self.scalar: Optional[torch.Tensor] = None    # Nadam's running product P of its momentum schedule: one float64
         self.t_dev = torch.zeros(1, dtype=torch.int64, device=device)
@@ -70,6 +73,15 @@ class FlatOptimizer:
             self.lr_dev.fill_(float(v))
             self._lr_host = float(v)
 
+    def take_state(self, other: "FlatOptimizer", elements: slice = slice(None)) -> None:
+        """m and v <- those `elements` of another instance's, with its step count and learning rate (a replica leaving an
+        ensemble); the learning rate arrives behind set_lr's back, so its host cache is void"""
+        self.m.copy_(other.m[elements])
+        self.v.copy_(other.v[elements])
+        self.t_dev.copy_(other.t_dev)
+        self.lr_dev.copy_(other.lr_dev)
+        self._lr_host = None
+
     def eval_lr(self, descriptor: dict) -> None:
         """lr_dev <- the schedule (fields of dib_lr_schedule) at the device step count, in a one-thread launch"""
         eval_lr(self.lib, descriptor, self.t_dev, self.lr_dev, self._stream())
@@ -88,25 +100,31 @@ class FlatOptimizer:
         check(self.lib.dib_optimizer_advance(opt.kind, byref(_hyper(opt)), _ptr(self.t_dev), _ptr(self._scalar(opt)),
                                              self._stream()), "dib_optimizer_advance")
 
-    def adam(self, params, grads, n: int, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0) -> None:
+    def adam(self, params, grads, n: int, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0, stream=None) -> None:
+        """stream: the launch stream a step already asked for (asking torch again costs about a microsecond)"""
         check(self.lib.dib_adam_step(_ptr(params), _ptr(grads), _ptr(self.m), _ptr(self.v), n, _ptr(self.lr_dev),
-                                     _ptr(self.t_dev), beta1, beta2, eps, float(grad_scale), self._stream()), "dib_adam_step")
+                                     _ptr(self.t_dev), beta1, beta2, eps, float(grad_scale),
+                                     stream if stream is not None else self._stream()), "dib_adam_step")
 
     def sgd(self, params, grads, n: int, grad_scale=1.0) -> None:
         check(self.lib.dib_sgd_step(_ptr(params), _ptr(grads), n, _ptr(self.lr_dev), float(grad_scale), self._stream()),
               "dib_sgd_step")
 
-    def reduce_adam(self, slabs, nsplit: int, params, grads, n: int, beta1=0.9, beta2=0.999, eps=1e-7) -> None:
-        """one launch: grads <- the fixed-order sum of `nsplit` slabs of n floats (none: grads as they are), Keras-Adam, t += 1"""
+    def reduce_adam(self, slabs, nsplit: int, params, grads, n: int, beta1=0.9, beta2=0.999, eps=1e-7, stream=None) -> None:
+        """one launch: grads <- the fixed-order sum of `nsplit` slabs of n floats (none: grads as they are), Keras-Adam, t += 1
+        (stream: as in adam)"""
         if self._sync is None:
             self._sync = torch.zeros(_lib.SYNC_WORDS, dtype=torch.int32, device=self.m.device)
         check(self.lib.dib_reduce_adam_step(_ptr(slabs), nsplit, n, _ptr(params), _ptr(grads),
                                             _ptr(self.m), _ptr(self.v), n, _ptr(self.lr_dev), _ptr(self.t_dev), beta1, beta2,
-                                            eps, 1.0, _ptr(self._sync), self._stream()), "dib_reduce_adam_step")
+                                            eps, 1.0, _ptr(self._sync), stream if stream is not None else self._stream()),
+              "dib_reduce_adam_step")
 
 
 class HoldsFlatOptimizer:
-    """For a class with a FlatOptimizer in `self.opt_state`: the names its state has always had, and the plain delegations"""
+    """For a class with a FlatOptimizer in `self.opt_state`: the names its state has always had, and the plain delegations.
+    The circuit and measurement models take the names and set_lr from it; their steps always launch Adam, so a rule bound with
+    set_optimizer is not something those steps honour."""
     adam_m = property(lambda self: self.opt_state.m, lambda self, t: setattr(self.opt_state, "m", t))
     adam_v = property(lambda self: self.opt_state.v, lambda self, t: setattr(self.opt_state, "v", t))
     opt_s2 = property(lambda self: self.opt_state.s2)

@@ -33,6 +33,14 @@ def _ptr_array3(t: torch.Tensor, offs):
     return (c_void_p * 3)(*([_ptr(t, o).value for o in offs] + [None] * (3 - len(offs))))
 
 
+def slab_rule(n: int):
+    """(nsplit, rows_per_split) of a weight gradient contracted over n batch rows: slabs of >= 64 rows (a multiple of 32), at
+    most 32 of them, summed in a fixed order afterwards"""
+    nsplit = max(1, min(32, n // 64))
+    rps = ((n + nsplit - 1) // nsplit + 31) // 32 * 32
+    return (n + rps - 1) // rps, rps
+
+
 class _Gemm:
     """One grouped-GEMM launch: a device descriptor table + base tensors.  A base tensor may be given by NAME when the table
     is built before its memory exists; `bind` resolves the names."""

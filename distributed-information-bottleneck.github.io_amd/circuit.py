@@ -12,7 +12,8 @@ Device path of one training step (include/dib_circuit.h, csrc/dib_circuit.h; the
 The sandwich bounds of all G channels over all evaluation batches are one dib_circuit_mi_bounds launch.  There is no CPU
 fallback: shapes outside the kernels' envelope raise ValueError before anything is launched.
 CircuitEnsemble trains R such models (other circuits, seeds, beta ramps) in lockstep on the batched twins of these entry points,
-the replica being a grid index: the same five launches per step whatever R."""
+the replica being a grid index: the same five launches per step whatever R.  Both classes are faces of _CircuitCore, which
+holds the state and everything around the C calls once; CircuitIB launches through the single entry points."""
 from __future__ import annotations
 
 import ctypes
@@ -23,7 +24,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._gemm_plan import _Gemm, _d, _ptr
+from ._flat_optimizer import FlatOptimizer, HoldsFlatOptimizer
+from ._gemm_plan import _Gemm, _d, _ptr, _ptr_array3, slab_rule
+from ._host import Carver, LibHandle
 from ._lib import ACTIVATIONS, check
 from .dense import _MlpDesc
 
@@ -176,13 +179,6 @@ def _initial_parameters(G, dims, w_off, sc_off, n_params, init_seed) -> np.ndarr
     return flat
 
 
-def _split_rule(B: int):
-    """the DenseStack split rule of the hidden layers' weight gradients over the batch: (nsplit, rows_per_split)"""
-    nsplit = max(1, min(32, B // 64))
-    rps = ((B + nsplit - 1) // nsplit + 31) // 32 * 32
-    return (B + rps - 1) // rps, rps
-
-
 def _evaluation_inputs(seed: int, n: int, nb: int) -> np.ndarray:
     """x [nb, n] = +-1: the seeded NumPy draw of utils.estimate_mi_sandwich_bounds for the 2-row dataset [[-1.], [1.]]"""
     rng = np.random.default_rng(seed)
@@ -190,13 +186,246 @@ def _evaluation_inputs(seed: int, n: int, nb: int) -> np.ndarray:
     return np.stack([data[rng.integers(0, 2, n)] for _ in range(nb)], 0)
 
 
-class _Eng:
-    def __init__(self, device):
-        self.lib = _lib.load_library()
-        self.device = torch.device(device)
+def _per_replica(value, R: int, what: str) -> List[float]:
+    """a scalar for every replica, or one entry per replica"""
+    if np.ndim(value) == 0:
+        return [float(value)] * R
+    vals = [float(v) for v in value]
+    if len(vals) != R:
+        raise ValueError(f"{what} takes a scalar or one value per replica ({R}); got {len(vals)}")
+    return vals
 
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+def _replica_seeds(seeds, R: int) -> List[int]:
+    """one evaluation seed per replica (default 0..R-1)"""
+    seeds = list(range(R)) if seeds is None else [int(s) for s in seeds]
+    if len(seeds) != R:
+        raise ValueError(f"seeds takes one seed per replica ({R})")
+    return seeds
+
+
+class _CircuitCore(HoldsFlatOptimizer):
+    """What CircuitIB and CircuitEnsemble are faces of: R replicas' gate counts, the flat layout and the predictor descriptor they
+    share, the flat state (params | grads and the optimizer's m | v, replica-major, n_params each) and, written once, the
+    workspace map of a batch size, the step, the evaluation of the channels' bounds, the fit loop and the access to a replica's
+    weights.  `batched` says which entry points launch them: the batched ones (the replica a grid index, any R), or - only for
+    R = 1 - the single ones, which are 1.6 us per step faster there (profiles/HISTORY.md).  The two differ only where a C call
+    is made; the faces translate their signatures (a truth table per call against tables at construction, scalars against
+    per-replica lists, one history against a list) into the core's."""
+
+    def _setup(self, gates, predictive_arch_spec, activation_function, init_seeds, noise_seeds, device, batched: bool) -> None:
+        self.gates, self.R, self.batched = [int(G) for G in gates], len(gates), bool(batched)
+        assert batched or self.R == 1
+        self.init_seeds, self.noise_seeds = init_seeds, noise_seeds
+        self.units, self.activation_function = [int(u) for u in predictive_arch_spec], activation_function
+        if activation_function not in ACTIVATIONS:
+            raise ValueError(f"unknown activation {activation_function!r}")
+        if not 1 <= len(self.units) <= 3:
+            raise ValueError(f"predictor {self.units}: 1-3 hidden layers")
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"{type(self).__name__} runs on the GPU (libdib_hip); no device is available")
+        self.eng = LibHandle(device)
+        lib, self.device = self.eng.lib, self.eng.device
+        self.lib, R = lib, self.R
+        self.dims, self.w_off, self.b_off, self.sc_off, self.n_params = _flat_layout(self.units)
+        self._desc = d = _predictor_desc(self.dims, self.w_off, self.b_off, activation_function)
+        if not (lib.dib_mlp_small_head_batched_supported(ctypes.byref(d), 1, R) if batched
+                else lib.dib_mlp_small_head_supported(ctypes.byref(d), 1)):
+            raise ValueError(f"predictor {self.units} / {activation_function}{f' x {R} replicas' if batched else ''} outside the "
+                             f"row-tile head kernel's envelope (dib_mlp_small_head{'_batched' if batched else ''}_supported): 1-3 "
+                             "hidden layers of widths multiple of 16 up to 1024, a piecewise-linear activation")
+        P = self.n_params
+        flat = np.concatenate([_initial_parameters(G, self.dims, self.w_off, self.sc_off, P, s)
+                               for G, s in zip(self.gates, init_seeds)])
+        self.params = torch.from_numpy(flat).to(self.device)
+        self.grads = torch.zeros(R * P, dtype=torch.float32, device=self.device)
+        self.opt_state = FlatOptimizer(lib, self.eng._stream, R * P, self.device)
+        self._G_c = (ctypes.c_int * R)(*self.gates)
+        self._seeds_c = (ctypes.c_uint64 * R)(*[s & (2 ** 64 - 1) for s in noise_seeds])
+        self.step = 0                 # the noise key's step of the next training batch (every replica's)
+        self._bufs: Dict[int, dict] = {}
+        self._mi_ws: Dict[tuple, torch.Tensor] = {}
+
+    # ---- one step ----------------------------------------------------------------------------
+    def _buffers(self, B: int) -> dict:
+        bf = self._bufs.get(B)
+        if bf is not None:
+            return bf
+        R, P, nh, c = self.R, self.n_params, len(self.dims) - 1, Carver(64)
+        c.take("u", R * B * U_LD)
+        c.take("g_u", R * B * U_LD)
+        for l in range(nh):
+            c.take(f"h{l}", R * B * self.dims[l][1])
+            c.take(f"g{l}", R * B * self.dims[l][1])
+        for name in ("y", "pred", "g_pred"):
+            c.take(name, R * B)
+        c.take("kl", R * (MAX_GATES + 1))
+        c.take("sums3", R * 3)
+        off, ws = c.off, torch.zeros(c.size, dtype=torch.float32, device=self.device)
+        # hidden layers' weight gradients: dW_l = a_l^T g_l (a_0 = u), the slab rule over the batch.  Split: every slab is a whole
+        # R * n_params gradient buffer; slab 0 also takes the output layers' gradients (head kernel) and the scalars' (circuit
+        # backward), the other slabs' regions of those stay zero - the optimizer's launch sums the slabs in order
+        nsplit, rps = slab_rule(B)
+        slabs = torch.zeros(nsplit * R * P, dtype=torch.float32, device=self.device) if nsplit > 1 else None
+        gt = slabs if nsplit > 1 else self.grads
+        descs = [_d(off["u" if l == 0 else f"h{l - 1}"] + r * B * self.dims[l][0], self.dims[l][0],
+                    off[f"g{l}"] + r * B * self.dims[l][1], self.dims[l][1], r * P + self.w_off[l], self.dims[l][1],
+                    self.dims[l][0], self.dims[l][1], B, bias_off=r * P + self.b_off[l]) for r in range(R) for l in range(nh)]
+        wgrad = _Gemm(2, descs, ws, ws, gt, bias_out=gt, nsplit=nsplit, rows_per_split=rps, split_stride=R * P)
+        wgrad.upload(self.device)
+        ptrs = lambda pre: _ptr_array3(ws, [off[f"{pre}{l}"] for l in range(nh)])
+        d, lib = ctypes.byref(self._desc), self.lib
+        head_bytes = lib.dib_mlp_small_head_batched_workspace_bytes(d, B, R) if self.batched \
+            else lib.dib_mlp_small_head_workspace_bytes(d, B)
+        rows = torch.zeros((R, B), dtype=torch.int32, device=self.device)
+        head_ws = torch.zeros(int(head_bytes) // 4 + 4, dtype=torch.float32, device=self.device)
+        # the arguments of a step that do not change from one step to the next, grouped as the entry points take them
+        p = {name: _ptr(ws, o) for name, o in off.items()}
+        args = dict(u=p["u"], y=p["y"], gt=_ptr(gt), gt_scalars=_ptr(gt, self.sc_off), fwd=(_ptr(rows), p["u"], p["y"], p["kl"]),
+                    head=(1, _lib.LOSS_KINDS["bce_logits"], 1.0 / B, ptrs("h"), ptrs("g"), p["pred"], p["g_pred"], p["g_u"], _ptr(gt)),
+                    head_out=(p["sums3"], _ptr(head_ws)), bwd=(_ptr(rows), p["g_u"]))
+        bf = dict(ws=ws, off=off, rows=rows, wgrad=wgrad, nsplit=nsplit, slabs=slabs, nslabs=nsplit if nsplit > 1 else 0, gt=gt,
+                  head_ws=head_ws, args=args)
+        self._bufs[B] = bf
+        return bf
+
+    def _check_batch(self, B: int) -> None:
+        lib, d, B = self.lib, ctypes.byref(self._desc), int(B)
+        if self.batched:
+            ok = lib.dib_circuit_batched_supported(self._G_c, self.R, B) and lib.dib_mlp_small_head_batched_supported(d, B, self.R)
+        else:
+            ok = lib.dib_circuit_supported(self.gates[0], B) and lib.dib_mlp_small_head_supported(d, B)
+        if not ok:
+            raise ValueError(f"batch size {B} outside the kernels' envelope 1 <= B <= {MAX_BATCH}")
+
+    def _launch_step(self, table_dev: Optional[torch.Tensor], B: int, betas, row_idx: Optional[torch.Tensor] = None) -> dict:
+        """one step of every replica.  The batched path takes the R floats `betas` and has its own tables (table_dev None); the
+        single path takes its truth table and ONE float, which makes this CircuitIB._step itself, with no call in between"""
+        lib, st, R, P = self.lib, self.eng._stream(), self.R, self.n_params
+        bf = self._buffers(B)
+        a, desc, params = bf["args"], ctypes.byref(self._desc), _ptr(self.params)
+        step, ri = self.step & 0xFFFFFFFF, _ptr(row_idx) if row_idx is not None else None
+        if self.batched:
+            tab = (_ptr(self._tables_dev), self._table_words, self._table_off_c, self._G_c, R, B, params, P, self.sc_off,
+                   self._seeds_c, step, (ctypes.c_float * R)(*betas))
+            check(lib.dib_circuit_fwd_batched(*tab, ri, *a["fwd"], st), "dib_circuit_fwd_batched")
+            check(lib.dib_mlp_small_head_step_batched(desc, params, P, a["u"], B, R, a["y"], *a["head"], P, *a["head_out"], st),
+                  "dib_mlp_small_head_step_batched")
+            bf["wgrad"].run(lib, st)
+            check(lib.dib_circuit_bwd_batched(*tab, *a["bwd"], a["gt"], P, st), "dib_circuit_bwd_batched")
+        else:
+            tab = (_ptr(table_dev), self.gates[0], B, _ptr(self.params, self.sc_off), self.noise_seeds[0], step, float(betas))
+            check(lib.dib_circuit_fwd(*tab, ri, *a["fwd"], st), "dib_circuit_fwd")
+            check(lib.dib_mlp_small_head_step(desc, params, a["u"], B, a["y"], *a["head"], *a["head_out"], st),
+                  "dib_mlp_small_head_step")
+            bf["wgrad"].run(lib, st)
+            check(lib.dib_circuit_bwd(*tab, *a["bwd"], a["gt_scalars"], st), "dib_circuit_bwd")
+        # grads = the fixed-order sum of the slabs (as given when unsplit), Keras Adam and the step count: one launch
+        self.opt_state.reduce_adam(bf["slabs"], bf["nslabs"], self.params, self.grads, R * P, stream=st)
+        self.step += 1
+        return bf
+
+    def _bce(self, bf) -> torch.Tensor:
+        o = bf["off"]["sums3"]
+        return bf["ws"][o: o + 3 * self.R].view(self.R, 3)[:, 2]
+
+    def _row_idx(self, row_idx) -> torch.Tensor:
+        ri = torch.as_tensor(np.asarray(row_idx) if not torch.is_tensor(row_idx) else row_idx)
+        return ri.to(self.device, torch.int32).contiguous()
+
+    def _last_step(self, r: int, B: int) -> dict:
+        bf, G = self._bufs[B], self.gates[r]
+
+        def v(name, n):
+            o = bf["off"][name] + r * n
+            return bf["ws"][o: o + n]
+
+        return {"rows": bf["rows"][r], "u": v("u", B * U_LD).view(B, U_LD), "y": v("y", B), "pred": v("pred", B),
+                "g_u": v("g_u", B * U_LD).view(B, U_LD), "kl": v("kl", MAX_GATES + 1)[:G + 1], "bce": v("sums3", 3)[2]}
+
+    # ---- information of the channels ---------------------------------------------------------------
+    def _mi_bounds(self, seeds: Sequence[int], n: int, nb: int, per_batch: bool) -> List[np.ndarray]:
+        """every replica's [G_r, 2] (lower, upper) in nats ([G_r, nb, 2] with per_batch), replica r on the inputs and the noise
+        key of seeds[r]: one launch, one read-back"""
+        lib, R, G0 = self.lib, self.R, self.gates[0]
+        need = int(lib.dib_circuit_mi_batched_workspace_bytes(R, n, nb) if self.batched else lib.dib_circuit_mi_workspace_bytes(G0, n, nb))
+        if need < 0:
+            raise ValueError(f"evaluation of {nb} batches of {n} points outside the kernel's envelope (n >= 2, 1 <= nb <= 65535)")
+        x = [_evaluation_inputs(s, n, nb) for s in seeds]
+        x = x[0] if R == 1 else np.stack(x, 0)              # [R][nb][n] (one replica: no copy)
+        ws = self._mi_ws.get((n, nb))
+        if ws is None:
+            ws = self._mi_ws[(n, nb)] = torch.zeros(need // 8 + 1, dtype=torch.float64, device=self.device)
+        xd = torch.from_numpy(x).to(self.device)
+        out = torch.empty((R, MAX_GATES if self.batched else G0, nb, 2), dtype=torch.float64, device=self.device)
+        if self.batched:
+            seeds_c = (ctypes.c_uint64 * R)(*[s & (2 ** 64 - 1) for s in seeds])
+            check(lib.dib_circuit_mi_bounds_batched(_ptr(self.params), self.n_params, self.sc_off, self._G_c, R, _ptr(xd), n, nb,
+                                                    seeds_c, _ptr(out), _ptr(ws), self.eng._stream()), "dib_circuit_mi_bounds_batched")
+        else:
+            check(lib.dib_circuit_mi_bounds(_ptr(self.params, self.sc_off), G0, _ptr(xd), n, nb, seeds[0] & (2 ** 64 - 1), _ptr(out),
+                                            _ptr(ws), self.eng._stream()), "dib_circuit_mi_bounds")
+        res = out.cpu().numpy()
+        return [res[r, :G].copy() if per_batch else np.mean(res[r, :G], axis=1) for r, G in enumerate(self.gates)]
+
+    # ---- training loop -----------------------------------------------------------------------
+    def _fit(self, table_dev, n: int, B: int, learning_rate: float, b0: Sequence[float], b1: Sequence[float],
+             evaluate_mutual_info_freq: Optional[int], seeds: Sequence[int]) -> List[dict]:
+        """the notebook's loop for every replica: one history per replica; the host synchronises only at evaluations"""
+        R = self.R
+        freq = int(evaluate_mutual_info_freq) if evaluate_mutual_info_freq is not None else max(1, n // 200)
+        self.set_lr(learning_rate)
+        hist = torch.zeros((n, R), dtype=torch.float32, device=self.device)
+        betas, bounds, steps = [], [[] for _ in range(R)], []
+        for step in range(n):
+            beta = [beta_schedule(step, n, b0[r], b1[r]) for r in range(R)]
+            betas.append(beta)
+            hist[step].copy_(self._bce(self._launch_step(table_dev, B, beta if self.batched else beta[0])))
+            if step % freq == 0:
+                ev = self._mi_bounds([evaluation_seed(s, step) for s in seeds], 1024, 8, False)
+                for r in range(R):
+                    bounds[r].append(ev[r] / np.log(2))
+                steps.append(step)
+        losses, betas = hist.cpu().numpy(), np.asarray(betas, dtype=np.float64).reshape(n, R)
+        return [{"bce_loss_series": losses[:, r].copy(), "beta": betas[:, r].copy(),
+                 "mutual_information_bounds": np.asarray(bounds[r]).reshape(-1, self.gates[r], 2),
+                 "evaluation_steps": np.asarray(steps), "evaluate_mutual_info_freq": freq} for r in range(R)]
+
+    # ---- a replica's weights -----------------------------------------------------------------
+    def _replica(self, r: int) -> int:
+        if not 0 <= int(r) < self.R:
+            raise IndexError(f"replica {r} of {self.R}")
+        return int(r)
+
+    def _region(self, r: int, off: int, n: int) -> torch.Tensor:
+        """n live parameters of replica r from `off` of its flat slice"""
+        o = self._replica(r) * self.n_params + off
+        return self.params[o: o + n]
+
+    def _read(self, r: int, off: int, *shape) -> np.ndarray:
+        return self._region(r, off, math.prod(shape)).detach().cpu().numpy().reshape(shape).copy()
+
+    def _write(self, r: int, off: int, a, *shape) -> None:
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(shape)   # (ValueError for weights of another shape)
+        self._region(r, off, a.size).copy_(torch.as_tensor(a.reshape(-1)))
+
+    def _predictor_weights(self, r: int) -> List[np.ndarray]:
+        """Keras-ordered [kernel, bias] per layer; the first kernel is [G_r, width] - its 16 - G_r zero pad rows of the device
+        layout are not part of it"""
+        out = []
+        for l, ((i, o), wo, bo) in enumerate(zip(self.dims, self.w_off, self.b_off)):
+            k = self._read(r, wo, i, o)
+            out += [k[:self.gates[r]].copy() if l == 0 else k, self._read(r, bo, o)]
+        return out
+
+    def _set_predictor_weights(self, r: int, weights: Sequence[np.ndarray]) -> None:
+        assert len(weights) == 2 * len(self.dims)
+        for l, ((i, o), wo, bo) in enumerate(zip(self.dims, self.w_off, self.b_off)):
+            k = np.asarray(weights[2 * l], dtype=np.float32)
+            if l == 0:
+                k = np.concatenate([k.reshape(self.gates[r], o), np.zeros((U_LD - self.gates[r], o), np.float32)], 0)
+            self._write(r, wo, k, i, o)
+            self._write(r, bo, weights[2 * l + 1], o)
 
 
 class _FeatureEncoder:
@@ -206,21 +435,19 @@ class _FeatureEncoder:
     def __init__(self, model: "CircuitIB", index: int):
         self._circuit, self.index = model, int(index)
 
-    def _views(self):
+    def _offsets(self):
         m = self._circuit
-        return m.scalars[self.index: self.index + 1], m.scalars[m.G + self.index: m.G + self.index + 1]
+        return m.sc_off + self.index, m.sc_off + m.G + self.index
 
     def get_weights(self) -> List[np.ndarray]:
-        s, lv = self._views()
-        return [s.detach().cpu().numpy().reshape(1, 1).copy(), lv.detach().cpu().numpy().reshape(1, 1).copy()]
+        return [self._circuit._read(0, o, 1, 1) for o in self._offsets()]
 
     def set_weights(self, weights: Sequence[np.ndarray]) -> None:
-        s, lv = self._views()
-        s.copy_(torch.as_tensor(np.asarray(weights[0], dtype=np.float32).reshape(1)))
-        lv.copy_(torch.as_tensor(np.asarray(weights[1], dtype=np.float32).reshape(1)))
+        for o, w in zip(self._offsets(), weights):
+            self._circuit._write(0, o, w, 1)
 
     def __call__(self, x) -> torch.Tensor:
-        s, lv = self._views()
+        s, lv = (self._circuit._region(0, o, 1) for o in self._offsets())
         x = torch.as_tensor(np.asarray(x, dtype=np.float32) if not torch.is_tensor(x) else x).to(self._circuit.device,
                                                                                                   torch.float32)
         x = x.reshape(-1, 1)
@@ -235,24 +462,13 @@ class _Predictor:
         self._m = model
 
     def get_weights(self) -> List[np.ndarray]:
-        m, out = self._m, []
-        for l in range(len(m.dims)):
-            k = m.kernel(l).detach().cpu().numpy()
-            out += [(k[:m.G] if l == 0 else k).copy(), m.bias(l).detach().cpu().numpy().copy()]
-        return out
+        return self._m._predictor_weights(0)
 
     def set_weights(self, weights: Sequence[np.ndarray]) -> None:
-        m = self._m
-        assert len(weights) == 2 * len(m.dims)
-        for l in range(len(m.dims)):
-            k = np.asarray(weights[2 * l], dtype=np.float32)
-            if l == 0:
-                k = np.concatenate([k, np.zeros((U_LD - m.G, k.shape[1]), np.float32)], 0)
-            m.kernel(l).copy_(torch.as_tensor(k))
-            m.bias(l).copy_(torch.as_tensor(np.asarray(weights[2 * l + 1], dtype=np.float32)))
+        self._m._set_predictor_weights(0, weights)
 
 
-class CircuitIB:
+class CircuitIB(_CircuitCore):
     """The Boolean-circuit notebook's model on the gfx950 kernels (cell 6 names)."""
 
     def __init__(self, number_input_gates: int, predictive_arch_spec=(256, 256, 256), activation_function: str = "leaky_relu",
@@ -260,43 +476,22 @@ class CircuitIB:
         G = int(number_input_gates)
         if not 1 <= G <= MAX_GATES:
             raise ValueError(f"number_input_gates {G} outside the kernels' envelope 1 <= G <= {MAX_GATES}")
-        if not torch.cuda.is_available():
-            raise RuntimeError("CircuitIB runs on the GPU (libdib_hip); no device is available")
-        self.G, self.noise_seed = G, int(noise_seed)
-        self.eng = _Eng(device)
-        self.lib, self.device = self.eng.lib, self.eng.device
-        units = [int(u) for u in predictive_arch_spec]
-        if activation_function not in ACTIVATIONS:
-            raise ValueError(f"unknown activation {activation_function!r}")
-        self.dims, self.w_off, self.b_off, self.sc_off, self.n_params = _flat_layout(units)
-        self._desc = d = _predictor_desc(self.dims, self.w_off, self.b_off, activation_function)
-        nh = len(units)
-        if not 1 <= nh <= 3 or not self.lib.dib_mlp_small_head_supported(ctypes.byref(d), 1):
-            raise ValueError(f"predictor {units} / {activation_function} outside the row-tile head kernel's envelope "
-                             "(dib_mlp_small_head_supported): 1-3 hidden layers of widths multiple of 16 up to 1024, a "
-                             "piecewise-linear activation")
-        flat = _initial_parameters(G, self.dims, self.w_off, self.sc_off, self.n_params, init_seed)
-        self.params = torch.from_numpy(flat).to(self.device)
-        z = lambda: torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
-        self.grads, self.adam_m, self.adam_v = z(), z(), z()
+        self.G = G
+        self._setup([G], predictive_arch_spec, activation_function, [int(init_seed)], [int(noise_seed)], device, batched=False)
         self.scalars = self.params[self.sc_off: self.sc_off + 2 * G]
-        self.t_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.lr_dev = torch.full((1,), 1e-3, dtype=torch.float32, device=self.device)
-        self._sync = torch.zeros(_lib.SYNC_WORDS, dtype=torch.int32, device=self.device)
         self.feature_encoders = [_FeatureEncoder(self, g) for g in range(G)]
         self.predictive_model = _Predictor(self)
-        self.step = 0                 # the noise key's step of the next training batch
-        self._bufs: Dict[int, dict] = {}
-        self._mi_ws: Dict[tuple, torch.Tensor] = {}
         self._table_key, self._table_dev = None, None
+
+    noise_seed = property(lambda self: self.noise_seeds[0], lambda self, s: self.noise_seeds.__setitem__(0, int(s)))
 
     # views
     def kernel(self, l):
         i, o = self.dims[l]
-        return self.params[self.w_off[l]: self.w_off[l] + i * o].view(i, o)
+        return self._region(0, self.w_off[l], i * o).view(i, o)
 
     def bias(self, l):
-        return self.params[self.b_off[l]: self.b_off[l] + self.dims[l][1]]
+        return self._region(0, self.b_off[l], self.dims[l][1])
 
     # ---- one step ----------------------------------------------------------------------------
     def _table(self, table) -> torch.Tensor:
@@ -309,78 +504,7 @@ class CircuitIB:
             self._table_key = key
         return self._table_dev
 
-    def _buffers(self, B: int) -> dict:
-        bf = self._bufs.get(B)
-        if bf is not None:
-            return bf
-        off, o = {}, 0
-
-        def take(name, cnt):
-            nonlocal o
-            off[name] = o
-            o = (o + int(cnt) + 63) // 64 * 64
-
-        nh = len(self.dims) - 1
-        take("u", B * U_LD)
-        take("g_u", B * U_LD)
-        for l in range(nh):
-            take(f"h{l}", B * self.dims[l][1])
-            take(f"g{l}", B * self.dims[l][1])
-        for name in ("y", "pred", "g_pred"):
-            take(name, B)
-        take("kl", self.G + 1)
-        take("sums3", 4)
-        ws = torch.zeros(o, dtype=torch.float32, device=self.device)
-        # hidden layers' weight gradients: dW_l = a_l^T g_l (a_0 = u), the DenseStack split rule over the batch.  Split: every
-        # slab is a whole gradient buffer; slab 0 also takes the output layer's gradient (head kernel) and the scalars'
-        # (dib_circuit_bwd), the other slabs' regions of those stay zero - the optimizer's launch sums the slabs in order
-        nsplit, rps = _split_rule(B)
-        slabs = torch.zeros(nsplit * self.n_params, dtype=torch.float32, device=self.device) if nsplit > 1 else None
-        gt = slabs if nsplit > 1 else self.grads
-        descs = [_d(off["u" if l == 0 else f"h{l - 1}"], self.dims[l][0], off[f"g{l}"], self.dims[l][1], self.w_off[l],
-                    self.dims[l][1], self.dims[l][0], self.dims[l][1], B, bias_off=self.b_off[l]) for l in range(nh)]
-        wgrad = _Gemm(2, descs, ws, ws, gt, bias_out=gt, nsplit=nsplit, rows_per_split=rps, split_stride=self.n_params)
-        wgrad.upload(self.device)
-        ptrs = lambda pre: (ctypes.c_void_p * 3)(*[_ptr(ws, off[f"{pre}{l}"]).value if l < nh else None for l in range(3)])
-        head_ws = torch.zeros(int(self.lib.dib_mlp_small_head_workspace_bytes(ctypes.byref(self._desc), B)) // 4 + 4,
-                              dtype=torch.float32, device=self.device)
-        bf = dict(ws=ws, off=off, rows=torch.zeros(B, dtype=torch.int32, device=self.device), wgrad=wgrad, nsplit=nsplit,
-                  slabs=slabs, gt=gt, h=ptrs("h"), g=ptrs("g"), head_ws=head_ws)
-        self._bufs[B] = bf
-        return bf
-
-    def _view(self, bf, name, n):
-        o = bf["off"][name]
-        return bf["ws"][o: o + n]
-
-    def _check_batch(self, B: int) -> None:
-        if not self.lib.dib_circuit_supported(self.G, int(B)) or not self.lib.dib_mlp_small_head_supported(ctypes.byref(self._desc),
-                                                                                                          int(B)):
-            raise ValueError(f"batch size {B} outside the kernels' envelope 1 <= B <= {MAX_BATCH}")
-
-    def _step(self, table_dev: torch.Tensor, B: int, beta: float, row_idx: Optional[torch.Tensor] = None) -> dict:
-        lib, st, G = self.lib, self.eng._stream(), self.G
-        bf = self._buffers(B)
-        ws, off = bf["ws"], bf["off"]
-        sc = _ptr(self.params, self.sc_off)
-        seed, step = self.noise_seed, self.step & 0xFFFFFFFF
-        check(lib.dib_circuit_fwd(_ptr(table_dev), G, B, sc, seed, step, float(beta), _ptr(row_idx) if row_idx is not None else None,
-                                  _ptr(bf["rows"]), _ptr(ws, off["u"]), _ptr(ws, off["y"]), _ptr(ws, off["kl"]), st), "dib_circuit_fwd")
-        check(lib.dib_mlp_small_head_step(ctypes.byref(self._desc), _ptr(self.params), _ptr(ws, off["u"]), B, _ptr(ws, off["y"]), 1,
-                                          _lib.LOSS_KINDS["bce_logits"], 1.0 / B, bf["h"], bf["g"], _ptr(ws, off["pred"]),
-                                          _ptr(ws, off["g_pred"]), _ptr(ws, off["g_u"]), _ptr(bf["gt"]), _ptr(ws, off["sums3"]),
-                                          _ptr(bf["head_ws"]), st), "dib_mlp_small_head_step")
-        bf["wgrad"].run(lib, st)
-        check(lib.dib_circuit_bwd(_ptr(table_dev), G, B, sc, seed, step, float(beta), _ptr(bf["rows"]), _ptr(ws, off["g_u"]),
-                                  _ptr(bf["gt"], self.sc_off), st), "dib_circuit_bwd")
-        # grads = the fixed-order sum of the slabs (as given when unsplit), Keras Adam and the step count: one launch
-        split = bf["nsplit"] > 1
-        check(lib.dib_reduce_adam_step(_ptr(bf["slabs"]) if split else None, bf["nsplit"] if split else 0, self.n_params,
-                                       _ptr(self.params), _ptr(self.grads), _ptr(self.adam_m), _ptr(self.adam_v), self.n_params,
-                                       _ptr(self.lr_dev), _ptr(self.t_dev), 0.9, 0.999, 1e-7, 1.0, _ptr(self._sync), st),
-              "dib_reduce_adam_step")
-        self.step += 1
-        return bf
+    _step = _CircuitCore._launch_step   # (table_dev, B, beta, row_idx=None)
 
     def train_step(self, truth_table, beta: float, batch_size: int = 512, row_idx=None) -> torch.Tensor:
         """cell 6 train_step: one batch drawn from the truth table ([2^G, G + 1] 0/1 rows), BCE + beta sum_g KL_g, Keras Adam.
@@ -389,23 +513,14 @@ class CircuitIB:
         B = int(batch_size) if row_idx is None else int(len(row_idx))
         self._check_batch(B)
         table = self._table(truth_table)
-        ri = None
-        if row_idx is not None:
-            ri = torch.as_tensor(np.asarray(row_idx) if not torch.is_tensor(row_idx) else row_idx).to(self.device, torch.int32)
-            ri = ri.contiguous()
-        bf = self._step(table, B, beta, ri)
-        o = bf["off"]["sums3"]
-        return bf["ws"][o + 2: o + 3].clone()[0]
+        ri = self._row_idx(row_idx) if row_idx is not None else None
+        bf = self._launch_step(table, B, beta, ri)
+        o = bf["off"]["sums3"] + 2                     # (_bce(bf)[0] with fewer torch calls: this call is host-bound)
+        return bf["ws"][o: o + 1].clone()[0]
 
     def last_step(self, batch_size: int) -> dict:
         """device views of the last step at this batch size: rows [B], u [B, 16], y [B], pred [B] (logits), g_u [B, 16], kl [G + 1]"""
-        bf, B = self._bufs[int(batch_size)], int(batch_size)
-        v = lambda name, n: self._view(bf, name, n)
-        return {"rows": bf["rows"], "u": v("u", B * U_LD).view(B, U_LD), "y": v("y", B), "pred": v("pred", B),
-                "g_u": v("g_u", B * U_LD).view(B, U_LD), "kl": v("kl", self.G + 1), "bce": v("sums3", 3)[2]}
-
-    def set_lr(self, learning_rate: float) -> None:
-        self.lr_dev.fill_(float(learning_rate))
+        return self._last_step(0, int(batch_size))
 
     # ---- information of the channels ---------------------------------------------------------------
     def estimate_channel_mi_bounds(self, seed: int = 0, evaluation_batch_size: int = 1024, number_evaluation_batches: int = 8,
@@ -413,21 +528,7 @@ class CircuitIB:
         """cell 6's estimate_mi_sandwich_bounds(feature_encoder, [[-1.], [1]]) for every gate at once: [G, 2] (lower, upper) in
         nats, the mean over the batches ([G, nb, 2] with per_batch).  The inputs of each batch are drawn by the seeded NumPy rule
         of utils.estimate_mi_sandwich_bounds for a 2-row dataset; one dib_circuit_mi_bounds launch."""
-        n, nb = int(evaluation_batch_size), int(number_evaluation_batches)
-        if self.lib.dib_circuit_mi_workspace_bytes(self.G, n, nb) < 0:
-            raise ValueError(f"evaluation of {nb} batches of {n} points outside the kernel's envelope (n >= 2, 1 <= nb <= 65535)")
-        x = _evaluation_inputs(seed, n, nb)
-        key = (n, nb)
-        ws = self._mi_ws.get(key)
-        if ws is None:
-            ws = self._mi_ws[key] = torch.zeros(int(self.lib.dib_circuit_mi_workspace_bytes(self.G, n, nb)) // 8 + 1,
-                                                dtype=torch.float64, device=self.device)
-        xd = torch.from_numpy(x).to(self.device)
-        out = torch.empty((self.G, nb, 2), dtype=torch.float64, device=self.device)
-        check(self.lib.dib_circuit_mi_bounds(_ptr(self.params, self.sc_off), self.G, _ptr(xd), n, nb, int(seed) & (2 ** 64 - 1),
-                                             _ptr(out), _ptr(ws), self.eng._stream()), "dib_circuit_mi_bounds")
-        r = out.cpu().numpy()
-        return r if per_batch else np.mean(r, axis=1)
+        return self._mi_bounds([int(seed)], int(evaluation_batch_size), int(number_evaluation_batches), per_batch)[0]
 
     # ---- training loop -----------------------------------------------------------------------
     def fit(self, truth_table, number_training_steps: int = 50_000, batch_size: int = 512, learning_rate: float = 1e-3,
@@ -437,39 +538,12 @@ class CircuitIB:
         included) estimate every channel's sandwich bounds (seed evaluation_seed(seed, step)).  Returns bce_loss_series [n]
         (nats), beta [n], mutual_information_bounds [n_eval, G, 2] (bits) and evaluation_steps.  The host synchronises only at
         evaluations."""
-        n = int(number_training_steps)
-        B = int(batch_size)
-        self._check_batch(B)
-        table = self._table(truth_table)
-        freq = int(evaluate_mutual_info_freq) if evaluate_mutual_info_freq is not None else max(1, n // 200)
-        self.set_lr(learning_rate)
-        hist = torch.zeros(n, dtype=torch.float32, device=self.device)
-        betas, bounds, steps = [], [], []
-        for step in range(n):
-            beta = beta_schedule(step, n, beta_start, beta_end)
-            betas.append(beta)
-            bf = self._step(table, B, beta)
-            o = bf["off"]["sums3"]
-            hist[step: step + 1].copy_(bf["ws"][o + 2: o + 3])
-            if step % freq == 0:
-                bounds.append(self.estimate_channel_mi_bounds(evaluation_seed(seed, step)) / np.log(2))
-                steps.append(step)
-        return {"bce_loss_series": hist.cpu().numpy(), "beta": np.asarray(betas, dtype=np.float64),
-                "mutual_information_bounds": np.asarray(bounds).reshape(-1, self.G, 2), "evaluation_steps": np.asarray(steps),
-                "evaluate_mutual_info_freq": freq}
+        self._check_batch(int(batch_size))
+        return self._fit(self._table(truth_table), int(number_training_steps), int(batch_size), learning_rate, [beta_start],
+                         [beta_end], evaluate_mutual_info_freq, [seed])[0]
 
 
-def _per_replica(value, R: int, what: str) -> List[float]:
-    """a scalar for every replica, or one entry per replica"""
-    if np.ndim(value) == 0:
-        return [float(value)] * R
-    vals = [float(v) for v in value]
-    if len(vals) != R:
-        raise ValueError(f"{what} takes a scalar or one value per replica ({R}); got {len(vals)}")
-    return vals
-
-
-class CircuitEnsemble:
+class CircuitEnsemble(_CircuitCore):
     """R CircuitIB models trained in lockstep: the six circuits of Fig. S1, or one circuit over seeds.  The model's shapes do not
     depend on the circuit (u is 16 columns wide for every G), so the replicas may differ in circuit, truth table, number of
     gates, seeds and beta ramp and still share every launch of a step:
@@ -480,7 +554,7 @@ class CircuitEnsemble:
         dib_reduce_adam_step              slab sum and Keras Adam over the R * n_params flat buffer
     and every replica's sandwich bounds are one dib_circuit_mi_bounds_batched launch.  Replica r starts from the parameters of
     CircuitIB(G_r, ..., init_seed=init_seeds[r], noise_seed=noise_seeds[r]) and draws that model's rows and noise at the same
-    step number; one learning rate and one Adam step count are shared.  params | grads | m | v are replica-major, each replica
+    step number; one learning rate and one Adam step count are shared.  params, grads, m and v are replica-major, each replica
     laid out like CircuitIB's flat buffer."""
 
     def __init__(self, truth_tables, predictive_arch_spec=(256, 256, 256), activation_function: str = "leaky_relu",
@@ -489,122 +563,22 @@ class CircuitEnsemble:
         R = len(tables)
         if R < 1:
             raise ValueError("a CircuitEnsemble takes at least one truth table (R >= 1)")
-        self.init_seeds = [int(s) for s in init_seeds] if init_seeds is not None else list(range(R))
-        self.noise_seeds = [int(s) for s in noise_seeds] if noise_seeds is not None else list(range(R))
-        if len(self.init_seeds) != R or len(self.noise_seeds) != R:
+        init_seeds = [int(s) for s in init_seeds] if init_seeds is not None else list(range(R))
+        noise_seeds = [int(s) for s in noise_seeds] if noise_seeds is not None else list(range(R))
+        if len(init_seeds) != R or len(noise_seeds) != R:
             raise ValueError(f"init_seeds and noise_seeds take one seed per replica ({R})")
         words = [pack_truth_table(t) for t in tables]          # ValueError unless [2^G, G + 1] 0/1 rows, 1 <= G <= 16
-        self.G = [t.shape[1] - 1 for t in tables]
-        self.units = [int(u) for u in predictive_arch_spec]
-        if activation_function not in ACTIVATIONS:
-            raise ValueError(f"unknown activation {activation_function!r}")
-        if not 1 <= len(self.units) <= 3:
-            raise ValueError(f"predictor {self.units}: 1-3 hidden layers")
-        if not torch.cuda.is_available():
-            raise RuntimeError("CircuitEnsemble runs on the GPU (libdib_hip); no device is available")
-        self.R, self.activation_function = R, activation_function
         self.tables = tables
-        self.eng = _Eng(device)
-        self.lib, self.device = self.eng.lib, self.eng.device
-        self.dims, self.w_off, self.b_off, self.sc_off, self.n_params = _flat_layout(self.units)
-        self._desc = d = _predictor_desc(self.dims, self.w_off, self.b_off, activation_function)
-        if not self.lib.dib_mlp_small_head_batched_supported(ctypes.byref(d), 1, R):
-            raise ValueError(f"predictor {self.units} / {activation_function} x {R} replicas outside the row-tile head kernel's "
-                             "envelope (dib_mlp_small_head_batched_supported)")
-        P = self.n_params
-        flat = np.concatenate([_initial_parameters(G, self.dims, self.w_off, self.sc_off, P, s)
-                               for G, s in zip(self.G, self.init_seeds)])
-        self._flat = torch.zeros(4 * R * P, dtype=torch.float32, device=self.device)
-        self.params, self.grads, self.adam_m, self.adam_v = (self._flat[i * R * P: (i + 1) * R * P] for i in range(4))
-        self.params.copy_(torch.from_numpy(flat))
+        self._setup([t.shape[1] - 1 for t in tables], predictive_arch_spec, activation_function, init_seeds, noise_seeds, device,
+                    batched=True)
+        self.G = self.gates
         offs = np.concatenate([[0], np.cumsum([w.shape[0] for w in words])])
         self._tables_dev = torch.from_numpy(np.concatenate(words).view(np.int32)).to(self.device)
         self._table_words = int(offs[-1])
         self._table_off_c = (ctypes.c_int64 * R)(*[int(o) for o in offs[:-1]])
-        self._G_c = (ctypes.c_int * R)(*self.G)
-        self._seeds_c = (ctypes.c_uint64 * R)(*[s & (2 ** 64 - 1) for s in self.noise_seeds])
-        self.t_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.lr_dev = torch.full((1,), 1e-3, dtype=torch.float32, device=self.device)
-        self._sync = torch.zeros(_lib.SYNC_WORDS, dtype=torch.int32, device=self.device)
-        self.step = 0                 # the noise key's step of the next training batch (every replica's)
-        self._bufs: Dict[int, dict] = {}
-        self._mi_ws: Dict[tuple, torch.Tensor] = {}
-
-    # ---- one step ----------------------------------------------------------------------------
-    def _buffers(self, B: int) -> dict:
-        bf = self._bufs.get(B)
-        if bf is not None:
-            return bf
-        R, P, off, o = self.R, self.n_params, {}, 0
-
-        def take(name, cnt):
-            nonlocal o
-            off[name] = o
-            o = (o + int(cnt) + 63) // 64 * 64
-
-        nh = len(self.dims) - 1
-        take("u", R * B * U_LD)
-        take("g_u", R * B * U_LD)
-        for l in range(nh):
-            take(f"h{l}", R * B * self.dims[l][1])
-            take(f"g{l}", R * B * self.dims[l][1])
-        for name in ("y", "pred", "g_pred"):
-            take(name, R * B)
-        take("kl", R * (MAX_GATES + 1))
-        take("sums3", R * 3)
-        ws = torch.zeros(o, dtype=torch.float32, device=self.device)
-        # CircuitIB's slab rule per replica: a slab is a whole R * n_params gradient buffer; slab 0 also takes the output
-        # layers' gradients (head kernel) and the scalars' (dib_circuit_bwd_batched)
-        nsplit, rps = _split_rule(B)
-        slabs = torch.zeros(nsplit * R * P, dtype=torch.float32, device=self.device) if nsplit > 1 else None
-        gt = slabs if nsplit > 1 else self.grads
-        descs = [_d(off["u" if l == 0 else f"h{l - 1}"] + r * B * self.dims[l][0], self.dims[l][0],
-                    off[f"g{l}"] + r * B * self.dims[l][1], self.dims[l][1], r * P + self.w_off[l], self.dims[l][1],
-                    self.dims[l][0], self.dims[l][1], B, bias_off=r * P + self.b_off[l]) for r in range(R) for l in range(nh)]
-        wgrad = _Gemm(2, descs, ws, ws, gt, bias_out=gt, nsplit=nsplit, rows_per_split=rps, split_stride=R * P)
-        wgrad.upload(self.device)
-        ptrs = lambda pre: (ctypes.c_void_p * 3)(*[_ptr(ws, off[f"{pre}{l}"]).value if l < nh else None for l in range(3)])
-        head_ws = torch.zeros(int(self.lib.dib_mlp_small_head_batched_workspace_bytes(ctypes.byref(self._desc), B, R)) // 4 + 4,
-                              dtype=torch.float32, device=self.device)
-        bf = dict(ws=ws, off=off, rows=torch.zeros((R, B), dtype=torch.int32, device=self.device), wgrad=wgrad, nsplit=nsplit,
-                  slabs=slabs, gt=gt, h=ptrs("h"), g=ptrs("g"), head_ws=head_ws)
-        self._bufs[B] = bf
-        return bf
-
-    def _check_batch(self, B: int) -> None:
-        if not self.lib.dib_circuit_batched_supported(self._G_c, self.R, int(B)) or \
-                not self.lib.dib_mlp_small_head_batched_supported(ctypes.byref(self._desc), int(B), self.R):
-            raise ValueError(f"batch size {B} outside the kernels' envelope 1 <= B <= {MAX_BATCH}")
 
     def _step(self, B: int, betas: Sequence[float], row_idx: Optional[torch.Tensor] = None) -> dict:
-        lib, st, R, P = self.lib, self.eng._stream(), self.R, self.n_params
-        bf = self._buffers(B)
-        ws, off = bf["ws"], bf["off"]
-        beta_c = (ctypes.c_float * R)(*betas)
-        step = self.step & 0xFFFFFFFF
-        tab = (_ptr(self._tables_dev), self._table_words, self._table_off_c, self._G_c, R, B, _ptr(self.params), P, self.sc_off,
-               self._seeds_c, step, beta_c)
-        check(lib.dib_circuit_fwd_batched(*tab, _ptr(row_idx) if row_idx is not None else None, _ptr(bf["rows"]), _ptr(ws, off["u"]),
-                                          _ptr(ws, off["y"]), _ptr(ws, off["kl"]), st), "dib_circuit_fwd_batched")
-        check(lib.dib_mlp_small_head_step_batched(ctypes.byref(self._desc), _ptr(self.params), P, _ptr(ws, off["u"]), B, R,
-                                                  _ptr(ws, off["y"]), 1, _lib.LOSS_KINDS["bce_logits"], 1.0 / B, bf["h"], bf["g"],
-                                                  _ptr(ws, off["pred"]), _ptr(ws, off["g_pred"]), _ptr(ws, off["g_u"]),
-                                                  _ptr(bf["gt"]), P, _ptr(ws, off["sums3"]), _ptr(bf["head_ws"]), st),
-              "dib_mlp_small_head_step_batched")
-        bf["wgrad"].run(lib, st)
-        check(lib.dib_circuit_bwd_batched(*tab, _ptr(bf["rows"]), _ptr(ws, off["g_u"]), _ptr(bf["gt"]), P, st),
-              "dib_circuit_bwd_batched")
-        split = bf["nsplit"] > 1
-        check(lib.dib_reduce_adam_step(_ptr(bf["slabs"]) if split else None, bf["nsplit"] if split else 0, R * P,
-                                       _ptr(self.params), _ptr(self.grads), _ptr(self.adam_m), _ptr(self.adam_v), R * P,
-                                       _ptr(self.lr_dev), _ptr(self.t_dev), 0.9, 0.999, 1e-7, 1.0, _ptr(self._sync), st),
-              "dib_reduce_adam_step")
-        self.step += 1
-        return bf
-
-    def _bce(self, bf) -> torch.Tensor:
-        o = bf["off"]["sums3"]
-        return bf["ws"][o: o + 3 * self.R].view(self.R, 3)[:, 2]
+        return self._launch_step(None, B, betas, row_idx)
 
     def train_step(self, beta, batch_size: int = 512, row_idx=None) -> torch.Tensor:
         """One step of every replica on a batch drawn from its own truth table.  beta: a float or R floats; row_idx ([R, B]
@@ -619,48 +593,19 @@ class CircuitEnsemble:
             B = int(ri.shape[1])
         self._check_batch(B)
         if ri is not None:
-            ri = torch.as_tensor(ri).to(self.device, torch.int32).contiguous()
-        return self._bce(self._step(B, betas, ri)).clone()
+            ri = self._row_idx(ri)
+        return self._bce(self._launch_step(None, B, betas, ri)).clone()
 
     def last_step(self, r: int, batch_size: int) -> dict:
         """device views of replica r's last step at this batch size, with the keys of CircuitIB.last_step"""
-        r = self._replica(r)
-        bf, B, G = self._bufs[int(batch_size)], int(batch_size), self.G[r]
-
-        def v(name, n):
-            o = bf["off"][name] + r * n
-            return bf["ws"][o: o + n]
-
-        return {"rows": bf["rows"][r], "u": v("u", B * U_LD).view(B, U_LD), "y": v("y", B), "pred": v("pred", B),
-                "g_u": v("g_u", B * U_LD).view(B, U_LD), "kl": v("kl", MAX_GATES + 1)[:G + 1], "bce": v("sums3", 3)[2]}
-
-    def set_lr(self, learning_rate: float) -> None:
-        self.lr_dev.fill_(float(learning_rate))
+        return self._last_step(self._replica(r), int(batch_size))
 
     # ---- information of the channels ---------------------------------------------------------------
     def estimate_channel_mi_bounds(self, seeds: Optional[Sequence[int]] = None, evaluation_batch_size: int = 1024,
                                    number_evaluation_batches: int = 8, per_batch: bool = False) -> List[np.ndarray]:
         """CircuitIB.estimate_channel_mi_bounds(seeds[r], ...) of every replica (default seeds 0..R-1) in ONE
         dib_circuit_mi_bounds_batched launch and one read-back: a list of [G_r, 2] arrays (nats; [G_r, nb, 2] with per_batch)"""
-        R, n, nb = self.R, int(evaluation_batch_size), int(number_evaluation_batches)
-        seeds = list(range(R)) if seeds is None else [int(s) for s in seeds]
-        if len(seeds) != R:
-            raise ValueError(f"seeds takes one seed per replica ({R})")
-        need = int(self.lib.dib_circuit_mi_batched_workspace_bytes(R, n, nb))
-        if need < 0:
-            raise ValueError(f"evaluation of {nb} batches of {n} points outside the kernel's envelope (n >= 2, 1 <= nb <= 65535)")
-        x = np.stack([_evaluation_inputs(s, n, nb) for s in seeds], 0)
-        ws = self._mi_ws.get((n, nb))
-        if ws is None:
-            ws = self._mi_ws[(n, nb)] = torch.zeros(need // 8 + 1, dtype=torch.float64, device=self.device)
-        xd = torch.from_numpy(x).to(self.device)
-        out = torch.empty((R, MAX_GATES, nb, 2), dtype=torch.float64, device=self.device)
-        seeds_c = (ctypes.c_uint64 * R)(*[s & (2 ** 64 - 1) for s in seeds])
-        check(self.lib.dib_circuit_mi_bounds_batched(_ptr(self.params), self.n_params, self.sc_off, self._G_c, R, _ptr(xd), n, nb,
-                                                     seeds_c, _ptr(out), _ptr(ws), self.eng._stream()),
-              "dib_circuit_mi_bounds_batched")
-        res = out.cpu().numpy()
-        return [res[r, :G].copy() if per_batch else np.mean(res[r, :G], axis=1) for r, G in enumerate(self.G)]
+        return self._mi_bounds(_replica_seeds(seeds, self.R), int(evaluation_batch_size), int(number_evaluation_batches), per_batch)
 
     # ---- training loop -----------------------------------------------------------------------
     def fit(self, number_training_steps: int = 50_000, batch_size: int = 512, learning_rate: float = 1e-3, beta_start=1e-3,
@@ -669,69 +614,32 @@ class CircuitEnsemble:
         beta_end (scalars, or one per replica), and where step % freq == 0 all replicas' bounds come from one launch, replica r
         with the inputs and noise key of CircuitIB.fit(seed=seeds[r]) (default seeds 0..R-1).  Returns one history per replica
         with the keys of CircuitIB.fit.  The host synchronises only at evaluations."""
-        R, n, B = self.R, int(number_training_steps), int(batch_size)
-        b0, b1 = _per_replica(beta_start, R, "beta_start"), _per_replica(beta_end, R, "beta_end")
-        seeds = list(range(R)) if seeds is None else [int(s) for s in seeds]
-        if len(seeds) != R:
-            raise ValueError(f"seeds takes one seed per replica ({R})")
-        self._check_batch(B)
-        freq = int(evaluate_mutual_info_freq) if evaluate_mutual_info_freq is not None else max(1, n // 200)
-        self.set_lr(learning_rate)
-        hist = torch.zeros((n, R), dtype=torch.float32, device=self.device)
-        betas, bounds, steps = [], [[] for _ in range(R)], []
-        for step in range(n):
-            beta = [beta_schedule(step, n, b0[r], b1[r]) for r in range(R)]
-            betas.append(beta)
-            hist[step].copy_(self._bce(self._step(B, beta)))
-            if step % freq == 0:
-                ev = self.estimate_channel_mi_bounds([evaluation_seed(s, step) for s in seeds])
-                for r in range(R):
-                    bounds[r].append(ev[r] / np.log(2))
-                steps.append(step)
-        losses, betas = hist.cpu().numpy(), np.asarray(betas, dtype=np.float64).reshape(n, R)
-        return [{"bce_loss_series": losses[:, r].copy(), "beta": betas[:, r].copy(),
-                 "mutual_information_bounds": np.asarray(bounds[r]).reshape(-1, self.G[r], 2), "evaluation_steps": np.asarray(steps),
-                 "evaluate_mutual_info_freq": freq} for r in range(R)]
+        b0, b1 = _per_replica(beta_start, self.R, "beta_start"), _per_replica(beta_end, self.R, "beta_end")
+        seeds = _replica_seeds(seeds, self.R)
+        self._check_batch(int(batch_size))
+        return self._fit(None, int(number_training_steps), int(batch_size), learning_rate, b0, b1, evaluate_mutual_info_freq, seeds)
 
     # ---- access to replicas ------------------------------------------------------------------
-    def _replica(self, r: int) -> int:
-        if not 0 <= int(r) < self.R:
-            raise IndexError(f"replica {r} of {self.R}")
-        return int(r)
-
     def replica_params(self, r: int) -> torch.Tensor:
         """replica r's slice [n_params] of the live parameter buffer (CircuitIB's layout)"""
-        r = self._replica(r)
-        return self.params[r * self.n_params: (r + 1) * self.n_params]
+        return self._region(r, 0, self.n_params)
 
     def get_weights(self, r: int) -> dict:
         """replica r: {"predictive_model": Keras-ordered [kernel, bias] per layer (the first kernel [G_r, width]),
         "mu_scaling": [G_r], "logvar": [G_r]}"""
-        p, G = self.replica_params(r).cpu().numpy(), self.G[self._replica(r)]
-        w = []
-        for l, ((i, o), wo, bo) in enumerate(zip(self.dims, self.w_off, self.b_off)):
-            k = p[wo: wo + i * o].reshape(i, o)
-            w += [(k[:G] if l == 0 else k).copy(), p[bo: bo + o].copy()]
-        return {"predictive_model": w, "mu_scaling": p[self.sc_off: self.sc_off + G].copy(),
-                "logvar": p[self.sc_off + G: self.sc_off + 2 * G].copy()}
+        G = self.G[self._replica(r)]
+        return {"predictive_model": self._predictor_weights(r), "mu_scaling": self._read(r, self.sc_off, G),
+                "logvar": self._read(r, self.sc_off + G, G)}
 
     def set_weights(self, r: int, weights: dict) -> None:
         """the counterpart of get_weights: any subset of its keys"""
-        live, G = self.replica_params(r), self.G[self._replica(r)]
-        put = lambda o, a: live[o: o + a.size].copy_(torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32).reshape(-1)))
+        G = self.G[self._replica(r)]
         if "predictive_model" in weights:
-            ws = weights["predictive_model"]
-            assert len(ws) == 2 * len(self.dims)
-            for l, ((i, o), wo, bo) in enumerate(zip(self.dims, self.w_off, self.b_off)):
-                k = np.asarray(ws[2 * l], dtype=np.float32)
-                if l == 0:
-                    k = np.concatenate([k.reshape(G, o), np.zeros((U_LD - G, o), np.float32)], 0)
-                put(wo, k.reshape(i, o))
-                put(bo, np.asarray(ws[2 * l + 1], dtype=np.float32).reshape(o))
+            self._set_predictor_weights(r, weights["predictive_model"])
         if "mu_scaling" in weights:
-            put(self.sc_off, np.asarray(weights["mu_scaling"], dtype=np.float32).reshape(G))
+            self._write(r, self.sc_off, weights["mu_scaling"], G)
         if "logvar" in weights:
-            put(self.sc_off + G, np.asarray(weights["logvar"], dtype=np.float32).reshape(G))
+            self._write(r, self.sc_off + G, weights["logvar"], G)
 
     def to_model(self, r: int) -> CircuitIB:
         """a CircuitIB holding replica r's parameters and Adam state (moments, step count, learning rate) at the current step:
@@ -740,8 +648,8 @@ class CircuitEnsemble:
         m = CircuitIB(self.G[r], self.units, self.activation_function, noise_seed=self.noise_seeds[r], init_seed=self.init_seeds[r],
                       device=self.device)
         sl = slice(r * self.n_params, (r + 1) * self.n_params)
-        m.params.copy_(self.params[sl]); m.grads.copy_(self.grads[sl])
-        m.adam_m.copy_(self.adam_m[sl]); m.adam_v.copy_(self.adam_v[sl])
-        m.t_dev.copy_(self.t_dev); m.lr_dev.copy_(self.lr_dev)
+        m.params.copy_(self.params[sl])
+        m.grads.copy_(self.grads[sl])
+        m.opt_state.take_state(self.opt_state, sl)
         m.step = self.step
         return m

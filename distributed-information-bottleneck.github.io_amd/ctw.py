@@ -226,6 +226,7 @@ def estimate_entropy_windows(symbols, starts, lengths, alphabet_size: int, backe
     import time
     import torch
     from . import _lib
+    from ._host import stream_ptr
     if not 1 <= alphabet_size <= _lib.CTW_DEVICE_MAX_ALPHABET:
         raise ValueError(f"alphabet_size {alphabet_size} outside the device estimator's envelope [1, {_lib.CTW_DEVICE_MAX_ALPHABET}]")
     if not torch.cuda.is_available():
@@ -260,7 +261,7 @@ def estimate_entropy_windows(symbols, starts, lengths, alphabet_size: int, backe
             _lib.check(lib.dib_ctw_device_estimate(c_void_p(sym.data_ptr()), n_symbols, s_.ctypes.data, l_.ctypes.data, n,
                                                    alphabet_size, cap, c_void_p(out[0].data_ptr()), c_void_p(out[1].data_ptr()),
                                                    c_void_p(out[2].data_ptr()), c_void_p(st.data_ptr()), c_void_p(ws.data_ptr()), nws,
-                                                   ctypes.byref(info), c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                                                   ctypes.byref(info), stream_ptr(dev)),
                        "dib_ctw_device_estimate")
         t0 = time.perf_counter()
         o, s = out.cpu().numpy(), st.cpu().numpy()

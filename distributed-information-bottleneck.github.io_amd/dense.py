@@ -17,7 +17,8 @@ import numpy as np
 import torch
 
 from ._flat_optimizer import FlatOptimizer, HoldsFlatOptimizer
-from ._gemm_plan import _Gemm, _d, _ptr, _ptr_array3
+from ._gemm_plan import _Gemm, _d, _ptr, _ptr_array3, slab_rule
+from ._host import Carver
 from ._lib import ACTIVATIONS, check
 
 
@@ -37,6 +38,38 @@ def _mlp_desc(w_off: Sequence[int], b_off: Sequence[int], widths: Sequence[int],
         d.w_off[l], d.b_off[l], d.width[l] = w_off[l], b_off[l], u
     d.n_hidden, d.in_dim, d.n_freq, d.act = len(widths) - 1, in_dim, n_freq, act
     return d
+
+
+def chain_plan(dims, w_off, b_off, act: int, n: int, params: torch.Tensor, device, carver: Carver, replicas: int = 1,
+               param_stride: int = 0, base: int = 0):
+    """The plan of a layer chain on n rows for `replicas` copies of it whose weights sit `param_stride` floats apart from
+    `base` in `params`, each laid out by (w_off, b_off): carves a0 (the input) and per layer l a{l+1} (its post-activation
+    output) and g{l+1} (dL/d its pre-activation; dL/d output for the last) out of `carver`, every region [replicas][n][width]
+    contiguous, and returns (ws, g, wgrad): the workspace, the uploaded launch records fwd{l} and dgrad{l} (one descriptor per
+    replica: the replica is the GROUP of a grouped launch) and the weight-gradient descriptors of every replica and layer, for
+    the caller to bind to its gradient buffer or slabs."""
+    R, L = replicas, len(dims)
+    carver.take("a0", R * n * dims[0][0])
+    for l, (_, wo) in enumerate(dims):
+        carver.take(f"a{l + 1}", R * n * wo)
+        carver.take(f"g{l + 1}", R * n * wo)
+    off, ws = carver.off, torch.zeros(carver.size, dtype=torch.float32, device=device)
+    pw = lambda r, l: r * param_stride + base + w_off[l]
+    pb = lambda r, l: r * param_stride + base + b_off[l]
+    g = {}
+    for l, (wi, wo) in enumerate(dims):
+        g[f"fwd{l}"] = _Gemm(0, [_d(off[f"a{l}"] + r * n * wi, wi, pw(r, l), wo, off[f"a{l + 1}"] + r * n * wo, wo, n, wo, wi,
+                                    bias_off=pb(r, l)) for r in range(R)], ws, params, ws, bias=params, act=act if l < L - 1 else 0)
+        if l > 0:   # dL/d(pre-activation of layer l-1) = (g_l @ W_l^T) * act'(a_l)
+            g[f"dgrad{l}"] = _Gemm(1, [_d(off[f"g{l + 1}"] + r * n * wo, wo, pw(r, l), wo, off[f"g{l}"] + r * n * wi, wi, n, wi, wo,
+                                          aux_off=off[f"a{l}"] + r * n * wi, ldaux=wi) for r in range(R)],
+                                   ws, params, ws, aux=ws, act=act)
+    for gg in g.values():
+        gg.upload(device)
+    # dW_l[i,o] = a_l^T @ g_{l+1}, bias gradients = column sums of g_{l+1}
+    wgrad = [_d(off[f"a{l}"] + r * n * wi, wi, off[f"g{l + 1}"] + r * n * wo, wo, pw(r, l), wo, wi, wo, n, bias_off=pb(r, l))
+             for r in range(R) for l, (wi, wo) in enumerate(dims)]
+    return ws, g, wgrad
 
 
 class DenseStack(HoldsFlatOptimizer):
@@ -83,40 +116,17 @@ class DenseStack(HoldsFlatOptimizer):
         pl = self._plans.get(n)
         if pl is not None:
             return pl
-        L = len(self.dims)
-        off, o = {}, 0
-
-        def take(name, cnt):
-            nonlocal o
-            off[name] = o
-            o = (o + int(cnt) + 3) // 4 * 4
-
-        take("y", n * self.input_dim)
-        take("a0", n * self.dims[0][0])                      # (positionally encoded) input
-        for l, (_, wo) in enumerate(self.dims):
-            take(f"a{l + 1}", n * wo)                        # post-activation output of layer l
-            take(f"g{l + 1}", n * wo)                        # dL/d(pre-activation of layer l) (= dL/d output for the last)
-        ws = torch.zeros(o, dtype=torch.float32, device=self.device)
-        # weight gradients: batch slabs of >= 64 rows (multiple of 32), <= 32 of them, fixed-order reduce
-        nsplit = max(1, min(32, n // 64))
-        rps = ((n + nsplit - 1) // nsplit + 31) // 32 * 32
-        nsplit = (n + rps - 1) // rps
+        L, c = len(self.dims), Carver(4)
+        c.take("y", n * self.input_dim)
+        ws, g, wgrad = chain_plan(self.dims, self.w_off, self.b_off, self.act, n, self.params, self.device, c)
+        off = c.off
+        # weight gradients: batch slabs (slab_rule), fixed-order reduce
+        nsplit, rps = slab_rule(n)
         slabs = torch.zeros(nsplit * self.n_params, dtype=torch.float32, device=self.device) if nsplit > 1 else None
         gt = slabs if nsplit > 1 else self.grads
-        g = {}
-        for l, (wi, wo) in enumerate(self.dims):
-            act = self.act if l < L - 1 else 0
-            g[f"fwd{l}"] = _Gemm(0, [_d(off[f"a{l}"], wi, self.w_off[l], wo, off[f"a{l + 1}"], wo, n, wo, wi,
-                                        bias_off=self.b_off[l])], ws, self.params, ws, bias=self.params, act=act)
-            if l > 0:   # dL/d(pre-activation of layer l-1) = (g_l @ W_l^T) * act'(a_l)
-                g[f"dgrad{l}"] = _Gemm(1, [_d(off[f"g{l + 1}"], wo, self.w_off[l], wo, off[f"g{l}"], wi, n, wi, wo,
-                                              aux_off=off[f"a{l}"], ldaux=wi)], ws, self.params, ws, aux=ws, act=self.act)
         # every layer's weight gradient in ONE grouped launch (independent products; the dgrad chain runs first)
-        g["wgrad_all"] = _Gemm(2, [_d(off[f"a{l}"], wi, off[f"g{l + 1}"], wo, self.w_off[l], wo, wi, wo, n, bias_off=self.b_off[l])
-                                  for l, (wi, wo) in enumerate(self.dims)], ws, ws, gt, bias_out=gt, nsplit=nsplit,
-                               rows_per_split=rps, split_stride=self.n_params)
-        for gg in g.values():
-            gg.upload(self.device)
+        g["wgrad_all"] = _Gemm(2, wgrad, ws, ws, gt, bias_out=gt, nsplit=nsplit, rows_per_split=rps, split_stride=self.n_params)
+        g["wgrad_all"].upload(self.device)
         if len(self._plans) >= 4:                             # train batch, validation batch, their tails
             self._plans.pop(next(iter(self._plans)))
         pl = self._plans[n] = dict(n=n, ws=ws, off=off, g=g, nsplit=nsplit, slabs=slabs, small=False)

@@ -16,7 +16,9 @@ There is no CPU fallback: a shape outside dib_measure_supported raises.
 
 MeasurementEnsemble trains R such models of one architecture in lockstep (the notebook's 20 repeats per number_states): the same
 step with the replica as the group of every grouped GEMM and as a grid index of dib_measure_fwd_batched / _bwd_batched and
-dib_infonce_fwd_bwd_batched, so that the number of launches of a step does not depend on R."""
+dib_infonce_fwd_bwd_batched, so that the number of launches of a step does not depend on R.  What the two classes do alike above
+the C ABI is written once: the layer-chain plan (dense.chain_plan), the optimizer state (FlatOptimizer), symbolize, and the
+preparation of fit; the two fit loops stay apart (other information kernels, and one retires replicas)."""
 from __future__ import annotations
 
 import ctypes
@@ -25,10 +27,12 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, ctw, utils
-from ._gemm_plan import _Gemm, _d, _ptr
+from . import ctw, utils
+from ._flat_optimizer import FlatOptimizer, HoldsFlatOptimizer
+from ._gemm_plan import _Gemm, _ptr, slab_rule
+from ._host import Carver, LibHandle as _Eng
 from ._lib import ACTIVATIONS, SIMILARITIES, check
-from .dense import DenseStack
+from .dense import DenseStack, chain_plan
 
 
 class _MeasureDesc(ctypes.Structure):
@@ -39,17 +43,6 @@ class _MeasureDesc(ctypes.Structure):
 
 
 assert ctypes.sizeof(_MeasureDesc) == 80
-
-
-class _Eng:
-    """what DenseStack needs of an engine: the library, the device and the launch stream"""
-
-    def __init__(self, device):
-        self.lib = _lib.load_library()
-        self.device = torch.device(device)
-
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
 
 class _Network:
@@ -94,7 +87,48 @@ def majority_symbols(assignments) -> np.ndarray:
     return np.uint8(np.mean(np.asarray(assignments), axis=0) > 0.5)
 
 
-class MeasurementIB:
+def _fit_setup(model, train_trajectory, learning_rate: float, evaluate_info_every: Optional[int], number_training_steps: int):
+    """what both fit loops begin with: the trajectory [n, d] on the device, the number of start indices it holds, the learning
+    rate set, and the evaluation period (default: a hundred evaluations per fit)"""
+    traj = torch.as_tensor(np.ascontiguousarray(np.asarray(train_trajectory, dtype=np.float32))).to(model.device)
+    if traj.dim() == 1:
+        traj = traj[:, None].contiguous()
+    model.set_lr(learning_rate)
+    every = evaluate_info_every if evaluate_info_every is not None else max(1, number_training_steps // 100)
+    return traj, traj.shape[0] - model.L, every
+
+
+def _info_out(batch_size: int, loss_prediction: float, L: int) -> float:
+    """cell 10: the InfoNCE bound on the predictive information in bits, per state of the sequence"""
+    return (np.log2(batch_size) - loss_prediction / np.log(2)) / L
+
+
+def _symbolize(model, enc_stack: DenseStack, vq_params: torch.Tensor, vq_off: int, data, number_averaging_logits, noise_vector,
+               seed, chunk_size, return_counts):
+    """cell 10's symbolisation with the IB encoder `enc_stack` and the packed VQ parameters at vq_params[vq_off:]: a fixed
+    noise table [K, E] (given, or drawn from a seeded NumPy generator) shared by every point; sym = uint8(mean_k argmax
+    VQ(mu + noise_k sigma) > 0.5).  One dib_measure_symbolize launch per chunk."""
+    x = torch.as_tensor(np.ascontiguousarray(np.asarray(data, dtype=np.float32))).to(model.device)
+    if x.dim() == 1:
+        x = x[:, None].contiguous()
+    if noise_vector is None:
+        noise_vector = np.random.default_rng(seed).standard_normal((int(number_averaging_logits), model.E))
+    noise = torch.as_tensor(np.asarray(noise_vector, dtype=np.float32).reshape(-1, model.E)).to(model.device).contiguous()
+    K, n = int(noise.shape[0]), int(x.shape[0])
+    sym = torch.empty(n, dtype=torch.uint8, device=model.device)
+    counts = torch.empty((n, model.A), dtype=torch.int32, device=model.device) if return_counts else None
+    st = model.eng._stream()
+    for c0 in range(0, n, int(chunk_size)):
+        c1 = min(n, c0 + int(chunk_size))
+        enc = enc_stack.forward(x[c0:c1])
+        check(model.lib.dib_measure_symbolize(ctypes.byref(model._desc), _ptr(vq_params, vq_off), _ptr(enc), c1 - c0, _ptr(noise), K,
+                                              _ptr(sym[c0:c1]), _ptr(counts[c0:c1]) if counts is not None else None, st),
+              "dib_measure_symbolize")
+    s = sym.cpu().numpy()
+    return (s, counts.cpu().numpy()) if return_counts else s
+
+
+class MeasurementIB(HoldsFlatOptimizer):
     """The chaos notebook's measurement-optimisation model on the gfx950 kernels (cell 10 hyperparameter names)."""
 
     def __init__(self, input_dimensionality: int, number_states: int = 12, alphabet_size: int = 2,
@@ -142,8 +176,8 @@ class MeasurementIB:
             offs.append(o)
             o += (s.n_params + 63) // 64 * 64
         self.n_params = o
-        z = lambda: torch.zeros(o, dtype=torch.float32, device=self.device)
-        self.params, self.grads, self.adam_m, self.adam_v = z(), z(), z(), z()
+        self.params, self.grads = (torch.zeros(o, dtype=torch.float32, device=self.device) for _ in range(2))
+        self.opt_state = FlatOptimizer(self.lib, self.eng._stream, o, self.device, learning_rate=3e-4)
         for s, off in zip(self._stacks, offs):
             self.params[off: off + s.n_params].copy_(s.params)
             s.params = self.params[off: off + s.n_params]
@@ -152,8 +186,6 @@ class MeasurementIB:
             s.adam_v = self.adam_v[off: off + s.n_params]
         for l in range(3):
             d.w_off[l], d.b_off[l] = self.vq.w_off[l], self.vq.b_off[l]
-        self.t_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.lr_dev = torch.full((1,), 3e-4, dtype=torch.float32, device=self.device)
         self.info_bott_encoder = _Network(self.ib, self, encoder=True)
         self.vector_quantization_network = _Network(self.vq, self)
         self.measurement_aggregator_network = _Network(self.agg, self)
@@ -219,8 +251,7 @@ class MeasurementIB:
                 check(lib.dib_reduce_splits(_ptr(vpl["slabs"]), self.vq.n_params, vpl["nsplit"], self.vq.n_params,
                                             _ptr(self.vq.grads), st), "dib_reduce_splits")
             self.ib.backward(g_enc)
-            check(lib.dib_adam_step(_ptr(self.params), _ptr(self.grads), _ptr(self.adam_m), _ptr(self.adam_v), self.n_params,
-                                    _ptr(self.lr_dev), _ptr(self.t_dev), 0.9, 0.999, 1e-7, 1.0, st), "dib_adam_step")
+            self.opt_state.adam(self.params, self.grads, self.n_params, stream=st)
             self.step += 1
         return bf
 
@@ -250,13 +281,8 @@ class MeasurementIB:
         """cell 10's loop: per-step log-linear beta annealing, uniformly drawn start indices (seeded NumPy generator), and
         every `evaluate_info_every` steps the sandwich bounds of I(U~; X) in bits (the loop stops once their mean reaches
         `info_stopping_point`).  The trajectory stays on the device; the host synchronises only at information evaluations."""
-        traj = torch.as_tensor(np.ascontiguousarray(np.asarray(train_trajectory, dtype=np.float32))).to(self.device)
-        if traj.dim() == 1:
-            traj = traj[:, None].contiguous()
-        n_starts = traj.shape[0] - self.L
+        traj, n_starts, every = _fit_setup(self, train_trajectory, learning_rate, evaluate_info_every, number_training_steps)
         rng = np.random.default_rng(seed)
-        self.lr_dev.fill_(float(learning_rate))
-        every = evaluate_info_every if evaluate_info_every is not None else max(1, number_training_steps // 100)
         hist = torch.zeros((number_training_steps, 2), dtype=torch.float32, device=self.device)
         out = {"loss": [], "info_in": [], "info_out": [], "beta": []}
         done = 0
@@ -273,8 +299,7 @@ class MeasurementIB:
                                                                     info_evaluation_batch_size, info_evaluation_number_batches,
                                                                     seed=step_num)) / np.log(2)
                 out["info_in"].append(info)
-                lpv = float(hist[step_num, 1])
-                out["info_out"].append((np.log2(batch_size) - lpv / np.log(2)) / self.L)
+                out["info_out"].append(_info_out(batch_size, float(hist[step_num, 1]), self.L))
                 if np.mean(info) >= info_stopping_point:
                     break
         out["loss"] = hist[:done, 0].cpu().numpy().tolist()
@@ -286,24 +311,8 @@ class MeasurementIB:
                   return_counts: bool = False):
         """cell 10's symbolisation: a fixed noise table [K, E] (given, or drawn from a seeded NumPy generator) shared by every
         point; sym = uint8(mean_k argmax VQ(mu + noise_k sigma) > 0.5).  One dib_measure_symbolize launch per chunk."""
-        x = torch.as_tensor(np.ascontiguousarray(np.asarray(data, dtype=np.float32))).to(self.device)
-        if x.dim() == 1:
-            x = x[:, None].contiguous()
-        if noise_vector is None:
-            noise_vector = np.random.default_rng(seed).standard_normal((int(number_averaging_logits), self.E))
-        noise = torch.as_tensor(np.asarray(noise_vector, dtype=np.float32).reshape(-1, self.E)).to(self.device).contiguous()
-        K, n = int(noise.shape[0]), int(x.shape[0])
-        sym = torch.empty(n, dtype=torch.uint8, device=self.device)
-        counts = torch.empty((n, self.A), dtype=torch.int32, device=self.device) if return_counts else None
-        st = self.eng._stream()
-        for c0 in range(0, n, int(chunk_size)):
-            c1 = min(n, c0 + int(chunk_size))
-            enc = self.ib.forward(x[c0:c1])
-            check(self.lib.dib_measure_symbolize(ctypes.byref(self._desc), _ptr(self.vq.params), _ptr(enc), c1 - c0, _ptr(noise), K,
-                                                 _ptr(sym[c0:c1]), _ptr(counts[c0:c1]) if counts is not None else None, st),
-                  "dib_measure_symbolize")
-        s = sym.cpu().numpy()
-        return (s, counts.cpu().numpy()) if return_counts else s
+        return _symbolize(self, self.ib, self.vq.params, 0, data, number_averaging_logits, noise_vector, seed, chunk_size,
+                          return_counts)
 
     def encode(self, x) -> torch.Tensor:
         """IB encoder output [n, 2E] (mu | logvar) on the device"""
@@ -382,38 +391,13 @@ class _EnsembleStack:
         pl = self._plans.get(n)
         if pl is not None:
             return pl
-        o, R, P, L = self.o, self.o.R, self.o.n_params, len(self.dims)
-        off, cur = {}, 0
-
-        def take(name, width):
-            nonlocal cur
-            off[name] = cur
-            cur = (cur + R * n * int(width) + 3) // 4 * 4
-
-        take("a0", self.dims[0][0])
-        for l, (_, wo) in enumerate(self.dims):
-            take(f"a{l + 1}", wo)                       # post-activation output of layer l, every replica
-            take(f"g{l + 1}", wo)                       # dL/d(pre-activation of layer l)
-        ws = torch.zeros(cur, dtype=torch.float32, device=o.device)
-        nsplit = max(1, min(32, n // 64))               # DenseStack's slab rule
-        rps = ((n + nsplit - 1) // nsplit + 31) // 32 * 32
-        nsplit = (n + rps - 1) // rps
-        pw = lambda r, l: r * P + self.base + self.w_off[l]
-        pb = lambda r, l: r * P + self.base + self.b_off[l]
-        g = {}
-        for l, (wi, wo) in enumerate(self.dims):
-            act = self.act if l < L - 1 else 0
-            g[f"fwd{l}"] = _Gemm(0, [_d(off[f"a{l}"] + r * n * wi, wi, pw(r, l), wo, off[f"a{l + 1}"] + r * n * wo, wo, n, wo, wi,
-                                        bias_off=pb(r, l)) for r in range(R)], ws, o.params, ws, bias=o.params, act=act)
-            if l > 0:
-                g[f"dgrad{l}"] = _Gemm(1, [_d(off[f"g{l + 1}"] + r * n * wo, wo, pw(r, l), wo, off[f"g{l}"] + r * n * wi, wi, n, wi, wo,
-                                              aux_off=off[f"a{l}"] + r * n * wi, ldaux=wi) for r in range(R)],
-                                       ws, o.params, ws, aux=ws, act=self.act)
-        for gg in g.values():
-            gg.upload(o.device)
+        o, c = self.o, Carver(4)
+        ws, g, wgrad_descs = chain_plan(self.dims, self.w_off, self.b_off, self.act, n, o.params, o.device, c, o.R, o.n_params,
+                                        self.base)
+        nsplit, rps = slab_rule(n)
         if len(self._plans) >= 4:
             self._plans.pop(next(iter(self._plans)))
-        pl = self._plans[n] = dict(n=n, ws=ws, off=off, g=g, nsplit=nsplit, rps=rps, wgrad={})
+        pl = self._plans[n] = dict(n=n, ws=ws, off=c.off, g=g, nsplit=nsplit, rps=rps, wgrad={}, wgrad_descs=wgrad_descs)
         return pl
 
     def wgrad(self, pl: dict, target: torch.Tensor, split_stride: int) -> _Gemm:
@@ -422,11 +406,8 @@ class _EnsembleStack:
         key = (target.data_ptr(), split_stride)
         gg = pl["wgrad"].get(key)
         if gg is None:
-            R, P, n, off = self.o.R, self.o.n_params, pl["n"], pl["off"]
-            gg = _Gemm(2, [_d(off[f"a{l}"] + r * n * wi, wi, off[f"g{l + 1}"] + r * n * wo, wo, r * P + self.base + self.w_off[l], wo,
-                              wi, wo, n, bias_off=r * P + self.base + self.b_off[l])
-                           for r in range(R) for l, (wi, wo) in enumerate(self.dims)], pl["ws"], pl["ws"], target, bias_out=target,
-                       nsplit=pl["nsplit"], rows_per_split=pl["rps"], split_stride=split_stride)
+            gg = _Gemm(2, pl["wgrad_descs"], pl["ws"], pl["ws"], target, bias_out=target, nsplit=pl["nsplit"],
+                       rows_per_split=pl["rps"], split_stride=split_stride)
             gg.upload(self.o.device)
             pl["wgrad"] = {key: gg}
         return gg
@@ -444,7 +425,7 @@ class _EnsembleStack:
             pl["g"][f"dgrad{l}"].run(self.o.lib, st)
 
 
-class MeasurementEnsemble:
+class MeasurementEnsemble(HoldsFlatOptimizer):
     """`replicas` MeasurementIB models of ONE architecture trained in lockstep - the notebook's "20 repeats per number_states":
     they differ in their initial weights, their noise seeds and the batches they draw, and share every launch of a step.
 
@@ -473,7 +454,8 @@ class MeasurementEnsemble:
             setattr(self, k, getattr(m0, k))
         P = self.n_params
         flat = torch.zeros(4 * R * P, dtype=torch.float32, device=self.device)
-        self.params, self.grads, self.adam_m, self.adam_v = (flat[i * R * P: (i + 1) * R * P] for i in range(4))
+        self.params, self.grads, m, v = (flat[i * R * P: (i + 1) * R * P] for i in range(4))
+        self.opt_state = FlatOptimizer(self.lib, self.eng._stream, R * P, self.device, learning_rate=3e-4, m=m, v=v)
         self._flat = flat
         bases = [int((s.params.data_ptr() - m0.params.data_ptr()) // 4) for s in m0._stacks]
         self.params[:P].copy_(m0.params)
@@ -487,12 +469,9 @@ class MeasurementEnsemble:
         self.ib, self.vq, self.agg, self.ref = (_EnsembleStack(self, s, b) for s, b in zip(m0._stacks, bases))
         self._nets = {"ib": self.ib, "vq": self.vq, "agg": self.agg, "ref": self.ref}
         self._seeds_c = (ctypes.c_uint64 * R)(*[s & (2 ** 64 - 1) for s in self.noise_seeds])
-        self.t_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.lr_dev = torch.full((1,), 3e-4, dtype=torch.float32, device=self.device)
         self.step, self.beta = 0, 10.0
         self.snapshots: Dict[int, torch.Tensor] = {}    # parameters of retired replicas (fit)
         self._bufs: Dict[int, dict] = {}
-        self._sym_ib: Optional[DenseStack] = None
 
     # ---- one step ----------------------------------------------------------------------------
     def _buffers(self, B: int) -> dict:
@@ -575,8 +554,7 @@ class MeasurementEnsemble:
             self.ib.wgrad(ib, target, stride).run(lib, st)
             if slabs is not None:
                 check(lib.dib_reduce_splits(_ptr(slabs), stride, bf["nsplit"], stride, _ptr(self.grads), st), "dib_reduce_splits")
-            check(lib.dib_adam_step(_ptr(self.params), _ptr(self.grads), _ptr(self.adam_m), _ptr(self.adam_v), stride,
-                                    _ptr(self.lr_dev), _ptr(self.t_dev), 0.9, 0.999, 1e-7, 1.0, st), "dib_adam_step")
+            self.opt_state.adam(self.params, self.grads, stride, stream=st)
             self.step += 1
         return bf
 
@@ -639,18 +617,13 @@ class MeasurementEnsemble:
         while the lockstep step goes on computing it so that nothing the others see changes.  Ends when every replica is
         retired or the steps run out.  Returns one history per replica with the keys of MeasurementIB.fit."""
         R = self.R
-        traj = torch.as_tensor(np.ascontiguousarray(np.asarray(train_trajectory, dtype=np.float32))).to(self.device)
-        if traj.dim() == 1:
-            traj = traj[:, None].contiguous()
-        n_starts = traj.shape[0] - self.L
         seeds = list(range(R)) if seeds is None else [int(s) for s in seeds]
         thr = np.broadcast_to(np.asarray(info_stopping_point, dtype=np.float64), (R,)) if np.ndim(info_stopping_point) == 0 \
             else np.asarray(info_stopping_point, dtype=np.float64)
         if len(seeds) != R or thr.shape != (R,):
             raise ValueError(f"seeds and info_stopping_point take one entry per replica ({R})")
+        traj, n_starts, every = _fit_setup(self, train_trajectory, learning_rate, evaluate_info_every, number_training_steps)
         rngs = [np.random.default_rng(s) for s in seeds]
-        self.lr_dev.fill_(float(learning_rate))
-        every = evaluate_info_every if evaluate_info_every is not None else max(1, number_training_steps // 100)
         ev = None
         if info_eval_data is not None:
             ev = np.asarray(info_eval_data, dtype=np.float32)
@@ -676,7 +649,7 @@ class MeasurementEnsemble:
                     if done[r] is not None:
                         continue
                     out[r]["info_in"].append(info[r])
-                    out[r]["info_out"].append((np.log2(batch_size) - float(lpv[r]) / np.log(2)) / self.L)
+                    out[r]["info_out"].append(_info_out(batch_size, float(lpv[r]), self.L))
                     if np.mean(info[r]) >= thr[r]:
                         done[r] = taken
                         self.snapshots[r] = self.params[r * self.n_params: (r + 1) * self.n_params].clone()
@@ -718,10 +691,14 @@ class MeasurementEnsemble:
 
     def to_model(self, r: int) -> MeasurementIB:
         """a MeasurementIB carrying replica r's weights (the snapshot if retired), noise seed and step: symbolize,
-        characterize_partition and the CTW back ends apply to it unchanged"""
+        characterize_partition and the CTW back ends apply to it unchanged.  A live replica also hands over its optimizer state
+        (Adam moments, step count, learning rate); a retired one does not - the moments went on moving after its snapshot -
+        and its model starts from a fresh one"""
         p = self._replica_params(r)
         m = MeasurementIB(init_seed=self.init_seeds[r], noise_seed=self.noise_seeds[r], **self._kwargs)
         m.params.copy_(p)
+        if int(r) not in self.snapshots:
+            m.opt_state.take_state(self.opt_state, slice(r * self.n_params, (r + 1) * self.n_params))
         m.step, m.beta = self.step, self.beta
         return m
 
@@ -730,23 +707,7 @@ class MeasurementEnsemble:
         """MeasurementIB.symbolize for replica r: its IB encoder on a DenseStack, dib_measure_symbolize on ITS packed VQ
         parameters where they lie in the ensemble's buffer (in its snapshot if retired)"""
         p = self._replica_params(r)
-        x = torch.as_tensor(np.ascontiguousarray(np.asarray(data, dtype=np.float32))).to(self.device)
-        if x.dim() == 1:
-            x = x[:, None].contiguous()
-        if noise_vector is None:
-            noise_vector = np.random.default_rng(seed).standard_normal((int(number_averaging_logits), self.E))
-        noise = torch.as_tensor(np.asarray(noise_vector, dtype=np.float32).reshape(-1, self.E)).to(self.device).contiguous()
-        K, n = int(noise.shape[0]), int(x.shape[0])
-        sym = torch.empty(n, dtype=torch.uint8, device=self.device)
-        counts = torch.empty((n, self.A), dtype=torch.int32, device=self.device) if return_counts else None
         enc_stack = self._template.ib                         # the template's encoder stack, loaded with replica r's weights
         enc_stack.params.copy_(p[self.ib.base: self.ib.base + self.ib.n_params])
-        st = self.eng._stream()
-        for c0 in range(0, n, int(chunk_size)):
-            c1 = min(n, c0 + int(chunk_size))
-            enc = enc_stack.forward(x[c0:c1])
-            check(self.lib.dib_measure_symbolize(ctypes.byref(self._desc), _ptr(p, self.vq.base), _ptr(enc), c1 - c0, _ptr(noise), K,
-                                                 _ptr(sym[c0:c1]), _ptr(counts[c0:c1]) if counts is not None else None, st),
-                  "dib_measure_symbolize")
-        s = sym.cpu().numpy()
-        return (s, counts.cpu().numpy()) if return_counts else s
+        return _symbolize(self, enc_stack, p, self.vq.base, data, number_averaging_logits, noise_vector, seed, chunk_size,
+                          return_counts)

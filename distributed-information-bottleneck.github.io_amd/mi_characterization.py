@@ -98,6 +98,7 @@ def monte_carlo_information(mus, logvars, mc_sample_size: int = 10_000, number_m
     One launch sequence while groups * mc_sample_size <= MAX_INDICES_PER_LAUNCH (the index upload: 64 MiB) and groups <= 65535."""
     import torch
 
+    from ._host import stream_ptr
     from ._lib import check, load_library
     tables, stacked = _tables(mus, logvars)
     S, N, E2 = tables.shape
@@ -116,7 +117,7 @@ def monte_carlo_information(mus, logvars, mc_sample_size: int = 10_000, number_m
     tab_d = torch.from_numpy(tables).to(dev)
     ws = torch.empty(need // 8 + 2, dtype=torch.float64, device=dev)
     means = torch.empty(G, dtype=torch.float64, device=dev)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = stream_ptr(dev)
     for g0 in range(0, G, per_launch):
         g1 = min(G, g0 + per_launch)
         src = np.stack([monte_carlo_source_rows(seed, group_offset + g, N, ns) for g in range(g0, g1)])

@@ -20,6 +20,7 @@ import torch
 
 from . import _lib, measurement
 from ._gemm_plan import _ptr
+from ._host import stream_ptr
 from ._lib import ACTIVATIONS, check
 from .dense import _MlpDesc
 
@@ -138,7 +139,7 @@ class RandomPartition:
         return x.to(self.device)
 
     def _launch(self, x: torch.Tensor, sym: torch.Tensor, logits: Optional[torch.Tensor], counts: Optional[torch.Tensor]) -> None:
-        st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        st = stream_ptr(self.device)
         check(self.lib.dib_partition_symbolize(ctypes.byref(self._desc), _ptr(self.params), ctypes.c_void_p(x.data_ptr()),
                                                int(x.dtype == torch.float64), x.stride(0), int(x.shape[0]),
                                                ctypes.c_void_p(sym.data_ptr()), _ptr(logits),

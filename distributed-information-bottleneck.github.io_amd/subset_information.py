@@ -211,6 +211,7 @@ def _host_bits(T, fb):
 def _device_bits(T, fb, K, device="cuda:0"):
     import torch
     from . import _lib
+    from ._host import stream_ptr
     if not torch.cuda.is_available():
         raise RuntimeError("subset_information(backend='device') runs on the GPU (libdib_hip); no device is available - "
                            "backend='host' is the float64 NumPy rule")
@@ -227,7 +228,7 @@ def _device_bits(T, fb, K, device="cuda:0"):
     widths = (ctypes.c_int * F)(*fb)
     _lib.check(lib.dib_subset_information(ctypes.c_void_p(counts.data_ptr()), B, K, widths, F, 0, 1 << F,
                                           ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
-                                          ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "dib_subset_information")
+                                          stream_ptr(dev)), "dib_subset_information")
     return out.cpu().numpy()
 
 

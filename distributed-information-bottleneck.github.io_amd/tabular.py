@@ -132,6 +132,7 @@ def quantile_transform_device(x, quantiles_t, references, output_distribution="n
     CUDA tensor [n_q]; out (optional) float32 [n, >= n_cols]; u64 (optional) float64 [n, n_cols] contiguous.  Returns out."""
     import torch
     from . import _lib
+    from ._host import stream_ptr
     lib = _lib.load_library()
     n_cols = int(quantiles_t.shape[0] if n_cols is None else n_cols)
     for t, dt in ((x, torch.float32), (quantiles_t, torch.float64), (references, torch.float64)):
@@ -148,7 +149,7 @@ def quantile_transform_device(x, quantiles_t, references, output_distribution="n
     p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
     _lib.check(lib.dib_quantile_transform(p(x), x.stride(0), x.shape[0], n_cols, p(quantiles_t), p(references), references.shape[0],
                                           _distribution(output_distribution), p(out), out.stride(0), p(u64),
-                                          ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)),
+                                          stream_ptr(x.device)),
                "dib_quantile_transform")
     return out
 

@@ -94,11 +94,10 @@ def mi_sandwich_rows(lib, device, enc_out, seed, step, feature):
     """dib_mi_sandwich_rows on one batch: enc_out is a float32 tensor [n, 2E] (mu | logvar) on `device`, the noise is keyed
     (seed, step, row, feature).  Returns (lower_rows, upper_rows) in nats as the two rows of one float64 device tensor [2, n];
     the launches go to the current stream and nothing waits for them."""
-    import ctypes
-
     import torch
 
     from ._gemm_plan import _ptr
+    from ._host import stream_ptr
     from ._lib import check
     enc_out = enc_out.contiguous()
     n, e = enc_out.shape[0], enc_out.shape[1] // 2
@@ -106,7 +105,7 @@ def mi_sandwich_rows(lib, device, enc_out, seed, step, feature):
     rows = torch.empty((2, n), dtype=torch.float64, device=device)
     check(lib.dib_mi_sandwich_rows(_ptr(enc_out), n, e, int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF, int(feature),
                                    _ptr(rows[0]), _ptr(rows[1]), _ptr(ws),
-                                   ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "dib_mi_sandwich_rows")
+                                   stream_ptr(device)), "dib_mi_sandwich_rows")
     return rows
 
 
@@ -132,6 +131,7 @@ def _sandwich_bounds_of_rows(table, rows, seed, step0=0):
 
     import torch
 
+    from ._host import stream_ptr
     from ._lib import check, load_library
     table = np.ascontiguousarray(table, dtype=np.float32)
     rows = np.ascontiguousarray(rows, dtype=np.int32)
@@ -152,7 +152,7 @@ def _sandwich_bounds_of_rows(table, rows, seed, step0=0):
     tab_d = torch.from_numpy(table).to(dev)
     ws = torch.empty(need // 8 + 2, dtype=torch.float64, device=dev)
     out = torch.empty((2, nb), dtype=torch.float64, device=dev)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = stream_ptr(dev)
     null = ctypes.c_void_p(0)
     for b0 in range(0, nb, per_launch):
         b1 = min(nb, b0 + per_launch)

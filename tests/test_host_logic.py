@@ -479,3 +479,20 @@ def test_batch_stream_is_tf_data_shuffle_buffer_over_the_repeating_sequential_st
     v0 = _BatchStream(5000, 128, [7, 0]).next_batches(40)
     v1 = _BatchStream(5000, 128, [7, 1]).next_batches(40)
     assert not np.array_equal(v0, v1) and v0.max() < 5000
+
+
+def test_slab_rule_values():
+    """worked by hand from the rule's three lines (slabs of >= 64 rows, a multiple of 32, at most 32 of them): e.g. 2049 rows ->
+    min(32, 2049 // 64) = 32 slabs of ceil(2049 / 32) = 65 -> 96 rows -> ceil(2049 / 96) = 22 slabs"""
+    from dib_amd._gemm_plan import slab_rule
+    want = {17: (1, 32), 127: (1, 128), 128: (2, 64), 160: (2, 96), 512: (8, 64), 2048: (32, 64), 2049: (22, 96)}
+    assert {n: slab_rule(n) for n in want} == want
+
+
+def test_carver_offsets_and_size():
+    from dib_amd._host import Carver
+    c = Carver(64)
+    assert [c.take("a", 17), c.take("b", 64), c.take("c", 65), c.take("d", 0)] == [0, 64, 128, 256] and c.size == 256
+    assert c.off == {"a": 0, "b": 64, "c": 128, "d": 256}
+    c = Carver(4)
+    assert [c.take("y", 5), c.take("a0", 3), c.take("a1", 4)] == [0, 8, 12] and c.size == 16
