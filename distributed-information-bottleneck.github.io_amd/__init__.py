@@ -11,6 +11,8 @@ from .set_transformer import SetTransformerDIB  # noqa: F401
 from .measurement import MeasurementEnsemble, MeasurementIB  # noqa: F401
 from . import circuit  # noqa: F401
 from .circuit import CircuitEnsemble, CircuitIB  # noqa: F401
+from . import ensemble  # noqa: F401
+from .ensemble import DistributedIBEnsemble  # noqa: F401
 from . import random_partition  # noqa: F401
 from .random_partition import RandomPartition  # noqa: F401
 from . import mi_characterization  # noqa: F401
@@ -21,5 +23,5 @@ from . import subset_information  # noqa: F401
 __all__ = ["DistributedIBNet", "DistributedIBModule", "InfoBottleneckAnnealingCallback", "SaveCompressionMatricesCallback",
            "InfoPerFeatureCallback", "PositionalEncoding", "Callback", "History", "models", "losses", "optimizers", "schedules", "data", "utils",
            "visualization", "ctw", "chaos_data", "set_transformer", "SetTransformerDIB", "measurement", "MeasurementIB", "MeasurementEnsemble",
-           "circuit", "CircuitIB", "CircuitEnsemble", "random_partition", "RandomPartition", "mi_characterization",
+           "circuit", "CircuitIB", "CircuitEnsemble", "ensemble", "DistributedIBEnsemble", "random_partition", "RandomPartition", "mi_characterization",
            "tabular", "TabularPreprocessor", "subset_information"]

@@ -268,6 +268,19 @@ SIGNATURES_CIRCUIT = {
                                               c_void_p, c_void_p]),
 }
 
+# include/dib_ensemble.h: the lockstep DistributedIBNet ensemble's kernels
+SIGNATURES_ENSEMBLE = {
+    "dib_ens_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "dib_ens_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
+    "dib_ens_posenc_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "dib_ens_reparam_kl_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                       c_void_p, c_void_p]),
+    "dib_ens_loss": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p,
+                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dib_ens_reparam_kl_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_int, c_void_p,
+                                       c_void_p]),
+}
+
 # include/dib_partition.h: the chaos notebook's random-MLP partitions
 SIGNATURES_PARTITION = {
     "dib_partition_supported": (c_int, [c_void_p]),
@@ -508,7 +521,7 @@ def _attach(lib):
         raise RuntimeError(f"libdib_hip ABI version {have} != {ABI_VERSION} expected by this binding ({getattr(lib, '_name', '?')}): "
                            "rebuild it (python -c 'import __graft_entry__ as g; g.build()' / tools/build_variant.sh)")
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_ST.items()) + list(SIGNATURES_MEASURE.items()) \
-            + list(SIGNATURES_CIRCUIT.items()) + list(SIGNATURES_PARTITION.items()) + list(SIGNATURES_MI_CHANNEL.items()) + list(SIGNATURES_MI_FEATURES.items()) \
+            + list(SIGNATURES_CIRCUIT.items()) + list(SIGNATURES_ENSEMBLE.items()) + list(SIGNATURES_PARTITION.items()) + list(SIGNATURES_MI_CHANNEL.items()) + list(SIGNATURES_MI_FEATURES.items()) \
             + list(SIGNATURES_COMPRESSION.items()) + list(SIGNATURES_OPTIMIZERS.items()) + list(SIGNATURES_LOSSES.items()) \
             + list(SIGNATURES_GRAD_TRANSFORM.items()) + list(SIGNATURES_TABULAR.items()) + list(SIGNATURES_SUBSETS.items()) \
             + list(SIGNATURES_CTW_DEVICE.items()):

@@ -82,6 +82,9 @@ def get_args(argv=None):
     p.add_argument('--table_valid_fraction', type=float, default=0.2)
     p.add_argument('--seed', type=int, default=0, help='noise / init / shuffle seed (the reference is unseeded)')
     p.add_argument('--verbose', type=_bool, default=False)
+    p.add_argument('--repeats', type=int, default=1,
+                   help='Keras path only: train this many replicas in lockstep (DistributedIBEnsemble) with seeds --seed + r; writes '
+                        'history_replicas.npz and one information plane with the replicas overlaid (not a reference flag)')
     return p.parse_args(argv)
 
 
@@ -139,9 +142,49 @@ def save_subset_information(dataset_dict, kl_series, loss_series, outdir, thresh
         predictive_information_out=info.entropy_y_bits - np.asarray(loss_series, dtype=np.float64), plot_start_ind=0)
 
 
+def check_repeats_args(args):
+    """--repeats N > 1 is the lockstep ensemble: the Keras path in one process, Adam at a constant rate, no per-epoch callbacks"""
+    if args.repeats < 1:
+        raise ValueError("--repeats must be at least 1")
+    if args.repeats == 1:
+        return
+    if args.infonce_loss:
+        raise ValueError("--repeats goes with the Keras path (not with --infonce_loss True)")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("--repeats trains all replicas in ONE process: run it without a multi-process launcher")
+    if args.save_compression_matrices_frequency > 0 or args.info_bounds_frequency > 0 or args.subset_information:
+        raise ValueError("--repeats: compression matrices, information bounds and the subset table are per-model callbacks; train "
+                         "with --repeats 1, or take a replica out of the ensemble with to_model(r)")
+
+
+def train_repeats(args, dataset_dict, optimizer, activation, number_epochs):
+    """--repeats N: N replicas with seeds --seed + r in lockstep; history_replicas.npz holds, per replica, the post-processed
+    series of postprocess_history (reference train.py:169-178), stacked on a leading replica axis"""
+    from . import ensemble, visualization
+    ens = ensemble.DistributedIBEnsemble(
+        args.repeats, dataset_dict['feature_dimensionalities'], args.feature_encoder_architecture,
+        args.integration_network_architecture, dataset_dict['output_dimensionality'],
+        use_positional_encoding=args.use_positional_encoding,
+        number_positional_encoding_frequencies=args.number_positional_encoding_frequencies, activation_fn=activation,
+        feature_embedding_dimension=args.feature_embedding_dimension, output_activation_fn=dataset_dict['output_activation_fn'],
+        noise_seed=args.seed, init_seed=args.seed, shuffle_seed=args.seed)
+    ens.compile(optimizer=optimizer, loss=dataset_dict['loss'], metrics=dataset_dict['metrics'])
+    histories = ens.fit(dataset_dict['x_train'], dataset_dict['y_train'], batch_size=args.batch_size, epochs=number_epochs,
+                        validation_data=(dataset_dict['x_valid'], dataset_dict['y_valid']), shuffle=True,
+                        beta_start=args.beta_start, beta_end=args.beta_end, number_pretraining_epochs=args.number_pretraining_epochs,
+                        number_annealing_epochs=args.number_annealing_epochs, verbose=args.verbose)
+    series = [postprocess_history(h.history, dataset_dict['number_features'], dataset_dict['loss_is_info_based']) for h in histories]
+    stacked = {k: np.stack([s[k] for s in series]) for k in series[0]}
+    print('Finished training.')
+    np.savez(os.path.join(args.artifact_outdir, 'history_replicas.npz'), seeds=np.int64(ens.noise_seeds), **stacked)
+    visualization.save_distributed_info_plane_replicas(stacked['kl_bits_validation'], stacked['loss_validation'], args.artifact_outdir)
+    return histories
+
+
 def main(argv=None):
     from . import data, models, optimizers, visualization
     args = get_args(argv)
+    check_repeats_args(args)
     import torch
     import torch.distributed as dist
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 and not dist.is_initialized():
@@ -217,6 +260,8 @@ def main(argv=None):
             if saver is not None:
                 save_compression_matrices_npz(saver, args.artifact_outdir)
         return out
+    if args.repeats > 1:
+        return train_repeats(args, dataset_dict, optimizer, activation, number_epochs)
     model.compile(optimizer=optimizer, loss=dataset_dict['loss'], metrics=dataset_dict['metrics'])
     callbacks = [models.InfoBottleneckAnnealingCallback(args.beta_start, args.beta_end, args.number_pretraining_epochs,
                                                         args.number_annealing_epochs)]

@@ -173,6 +173,41 @@ def save_distributed_info_plane(kl_series, loss_series, outdir, entropy_y=None):
     return saveto
 
 
+def save_distributed_info_plane_replicas(kl_series, loss_series, outdir, entropy_y=None):
+    """save_distributed_info_plane for R replicas of one model (train.py --repeats) overlaid in one figure: kl_series
+    [R, epochs, F] in bits, loss_series [R, epochs].  Every replica's curve (total KL against the task loss) is drawn thin and
+    black, its per-feature KL thin on the twin axis in the feature's colour, with the sieve and the starting point of
+    save_distributed_info_plane.  Writes distributed_info_plane_replicas.png."""
+    kl_series, loss_series = np.asarray(kl_series), np.asarray(loss_series)
+    R, epochs, number_features = kl_series.shape
+    desired = min(1000, epochs)
+    sieve = max(1, epochs // desired)
+    start = desired // 2
+    lims = [0, 15]
+    plt = _plt()
+    fig = plt.figure(figsize=(8, 4))
+    ax = fig.gca()
+    ax2 = ax.twinx() if number_features > 1 else None
+    for r in range(R):
+        parts = kl_series[r, ::sieve]
+        full = np.sum(parts, axis=-1)
+        ax.plot(full[start:], loss_series[r, ::sieve][start:], lw=1.5, color='k', alpha=0.6)
+        if ax2 is not None:
+            for f in range(number_features):
+                ax2.plot(full[start:], parts[start:, f], color=default_mpl_colors[f % len(default_mpl_colors)], lw=1.5, alpha=0.6)
+    if entropy_y is not None:
+        ax.plot(lims, [entropy_y] * 2, 'k:')
+    ax.set_xlim(lims)
+    if ax2 is not None:
+        ax.set_zorder(ax2.get_zorder() + 1)
+        ax.patch.set_visible(False)
+    os.makedirs(outdir, exist_ok=True)
+    saveto = os.path.join(outdir, 'distributed_info_plane_replicas.png')
+    fig.savefig(saveto, dpi=150)
+    plt.close(fig)
+    return saveto
+
+
 def save_distributed_info_plane_mi(information, loss_series, outdir, entropy_y=None):
     """The distributed information plane in mutual-information bounds instead of KL: `information` is History.information of
     DistributedIBNet.fit(track_information=...) - "bounds" [n_evals, F, 2] (InfoNCE lower, leave-one-out upper) in nats, "epochs"

@@ -67,6 +67,11 @@ ORACLE_TESTS = {
         "test_mi_bounds_batched_equal_the_single_kernel_and_compute_batch"},
     "test_gpu_circuit_ensemble.py": {
         "test_step_of_every_replica_matches_oracle", "test_thirty_adam_steps_through_per_replica_beta_ramps_match_oracle"},
+    "test_gpu_dib_ensemble_kernels.py": {
+        "test_reparam_forward_and_backward", "test_loss_and_history_sums", "test_posenc_rows_gathers_every_replica_and_feature"},
+    "test_gpu_dib_ensemble.py": {
+        "test_every_replicas_history_matches_the_oracle_fit_with_its_seeds_and_ramp", "test_gradients_of_both_replicas_match_the_oracle",
+        "test_to_model_continues_the_replica_and_weight_access_round_trips", "test_an_mse_pair_with_two_outputs_matches_the_oracle"},
     "test_gpu_random_partition.py": {
         "test_kernel_matches_oracle_across_the_envelope", "test_duplicated_and_negated_columns_go_to_the_lower_index",
         "test_notebook_configurations_match_the_oracle", "test_logistic_generating_partition_known_answer"},
@@ -181,6 +186,8 @@ EQUIVALENCE_TESTS = {
     "test_gpu_circuit_ensemble.py": {
         "test_one_replica_equals_the_single_model_bit_for_bit", "test_a_replica_does_not_see_the_others",
         "test_fit_is_reproducible_and_evaluates_like_the_single_model", "test_to_model_continues_a_replica_with_the_same_bits"},
+    "test_gpu_dib_ensemble_kernels.py": {"test_forward_reproduces_a_single_engines_u_bit_for_bit"},
+    "test_gpu_dib_ensemble.py": {"test_a_replica_does_not_see_the_others"},
     "test_gpu_ctw_levels.py": {
         "test_chunks_do_not_change_the_bits_and_an_overflowing_window_goes_to_the_host",
         "test_entropy_rate_fit_on_the_device_backend", "test_random_partition_characterize_keeps_the_symbols_on_the_device"},
